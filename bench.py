@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- embedded-SCF cycles/s (+ active-ERI transform GFLOP/s) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one cycle of the product's own ``nbed_amd.scf.huzinaga_scf`` (fused GPU path;
@@ -16,9 +16,15 @@ the largest single-GPU configuration): N_AO = 148, (33,33) occupied, 20 environm
 projected out -> (13,13) active electrons, n = 128 embedded MOs for the transform.
 The N_AO = 2000 headline config does not fit one GPU (a dense (pq|rs) is 128 TB).
 
-After the timed SCF cycles the same run times the AO->active-MO four-index transform
-(3 unique spin blocks of HamiltonianBuilder, nbed/ham_builder.py:119-124) and reports it
-under "transform".  rank 0 prints ONE JSON line.
+A plain run sets up, warms up (one untimed call of the path, then the W warm-up cycles of the
+timed call), times the K cycles and prints the line: the headline value, the J/K kernel's
+roofline from HIP events inside the timed cycles, the per-cycle breakdown.  With
+``--full`` the same run goes on to the secondary legs: the AO->active-MO four-index transform
+(3 unique spin blocks of HamiltonianBuilder, nbed/ham_builder.py:119-124) under "transform",
+time to solution, the mu-shift projector, the N_AO = 2000 samples, the scaling workloads, the
+real molecule, the small configurations, the CPU baselines and the multi-GPU collectives; a
+plain run reports those keys as null.  ``--dump-outputs DIR`` writes the arrays the timed run
+returned (last cycle) as DIR/<name>.npy.  rank 0 prints ONE JSON line.
 
 Multi-GPU (strong scaling, fixed problem): the first AO index of (pq|rs) is sharded over
 the ranks (each rank generates only its slab); every cycle all-gathers the J/K row slabs
@@ -68,7 +74,41 @@ def parse_args():
     ap.add_argument("--jk-event-every", type=int, default=4,
                     help="HIP events bracket the J/K kernel of one timed cycle in this many (1 = every cycle)")
     ap.add_argument("--cpu-cycles", type=int, default=8)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (time to solution, mu-shift, transform, N_AO=2000 samples, scaling "
+                         "workloads, real molecule, small configs, CPU baselines, multi-GPU collectives); the --no-* flags "
+                         "drop single legs of it.  Without it the run times the headline SCF cycles only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed SCF run returned (its last cycle's MO coefficients, MO energies, density "
+                         "and Huzinaga operator) as DIR/<name>.npy (bench_outputs/ is ignored by git)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if not args.full:  # a plain run measures the headline figure only
+        for leg in SECONDARY_LEGS:
+            setattr(args, f"no_{leg}", True)
+    return args
+
+
+# the legs a plain run leaves out (each one's --no-<leg> flag; --full runs them)
+SECONDARY_LEGS = ("cpu_baseline", "transform", "n2000", "tts", "mu", "real", "small", "scaling", "df")
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """Each array as ``out_dir/<name>.npy`` in float64.  An array over its share of DUMP_LIMIT_BYTES is written as a
+    fixed sample: the flat elements at indices drawn without replacement by a generator of fixed seed, in index order."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(20250829).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def host_cores() -> int:
@@ -770,6 +810,15 @@ def main():
                                "set-up and results included (the packed integrals are resident inputs)",
                    "dm_change_last_cycle": float(hist_c[-1][1]), "scf_restarts": list(hist_c.info.get("restarts", []))}
         del mf_c
+    else:
+        # warm-up of the process: the untimed first call the legs above make otherwise (one-off costs of the process --
+        # first-touch workspaces, the path the results come back to the host through -- stay out of the timed run)
+        mf_w = GpuUHF(Mole(N, pr["nelec"]), pr["S"], pr["hcore"], eri, backend=be, shards=shards,
+                      eri_packed=mf.eri_packed_device())
+        mf_w.conv_tol, mf_w.max_cycle = 1e-6, 50
+        huzinaga_scf(mf_w, pr["V_emb"], pr["D_env"], dm_conv_tol=1e-6, use_DIIS=True)
+        barrier()
+        del mf_w
 
     mf.conv_tol = -1.0  # the stopping rule can never fire: exactly max_cycle cycles run
     barrier()
@@ -801,10 +850,14 @@ def main():
 
     if os.environ.get("NBED_BENCH_POISON_LDS") == "1":  # (debug knob: every CU's LDS holds NaN when the run starts)
         be.debug_fill_lds(float("nan"))
-    huzinaga_scf(mf, pr["V_emb"], pr["D_env"], use_DIIS=True, history=hist, callback=on_cycle)
+    scf_out = huzinaga_scf(mf, pr["V_emb"], pr["D_env"], use_DIIS=True, history=hist, callback=on_cycle)
     barrier()
     dt = time.perf_counter() - clock["t0"]
     be.profile(False)
+    if args.dump_outputs and rank == 0:  # (host arrays: what the caller of the timed run receives)
+        mo_coeff, mo_energy, dm, hz, _conv = scf_out
+        dump_outputs(args.dump_outputs, {"mo_coeff": mo_coeff, "mo_energy": mo_energy, "dm": dm, "huzinaga_operator": hz})
+    del scf_out
     scf_restarts = list(hist.info.get("restarts", []))
     one_call = bool(hist.info.get("cycle_call"))
     hist = hist[args.warmup:]
@@ -1086,7 +1139,7 @@ def main():
     # ---------------- what a scaling curve needs to be read (every rank takes part: collectives): per-rank slab bytes
     # and J/K kernel time, the two collectives of the path timed on their own, the replicated remainder of a cycle
     multi = None
-    if distributed:
+    if distributed and args.full:
         from nbed_amd.dist import Shards as _Shards
 
         per_rank = gather_per_rank({"rank": rank, "slab_rows": [int(shards.lo), int(shards.hi)],
@@ -1179,6 +1232,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": bool(args.full),
             "config": {
                 "workload": f"synthetic octane/6-31G*-shaped embedded UHF (BASELINE configs[2]): N_AO={N}, "
                             f"n_occ=({args.nocc},{args.nocc}), n_env={args.nenv}, n_act_mo={n_act}; (pq|rs) in HBM"

@@ -109,8 +109,8 @@ def test_bench_child_process_over_single_rank_rccl(tmp_path):
     torch.cuda.empty_cache()
     env = dict(os.environ, NBED_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), RANK="0",
                WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, str(HERE.parent / "bench.py"), "--no-real", "--no-n2000", "--no-small", "--no-cpu-baseline",
-           "--no-tts", "--steps", "3"]
+    cmd = [sys.executable, str(HERE.parent / "bench.py"), "--full", "--no-real", "--no-n2000", "--no-small",
+           "--no-cpu-baseline", "--no-tts", "--steps", "3"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

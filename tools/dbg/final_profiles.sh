@@ -5,10 +5,10 @@ export PYTHONPATH=$R
 O=$R/gpurun_out/r04final
 mkdir -p $O
 # 1. the bench line, plain
-python $R/bench.py --steps 20 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err
 echo "bench done"
 # 2. the same command under rocprofv3 --kernel-trace --stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --steps 20 --warmup 5 > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err || true
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err || true
 cp $(ls $O/trace/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv
 python $R/tools/cycle_gaps.py $(ls $O/trace/*kernel_trace.csv | head -1) > $O/cycle_gaps.txt 2>&1 || true
 rm -rf $O/trace
