@@ -4,8 +4,15 @@
 // are mutually orthogonal, G = A V; then sigma_j = ||g_j|| and the accumulated V holds the
 // right singular vectors, including an orthonormal basis of the null space when m < n
 // (np.linalg.svd full_matrices=True semantics, which spade.py:132-134 relies on).
-// One-sided Jacobi keeps tiny singular values to high RELATIVE accuracy, which the
-// `sigma >= 1e-15` shell test of concentric.py:164,211 depends on.
+// Accuracy (Demmel & Veselic 1992): with floor = max(m,n) eps ||A||_F, every sigma above the floor
+// comes out to high RELATIVE accuracy -- O(max(m,n) eps) times the condition number of A with its
+// columns scaled to unit length, not of A -- and every sigma at or below it to ABSOLUTE accuracy
+// floor: a pair with a column at or below the floor is not rotated (that column is numerically
+// zero).  The `sigma >= 1e-15` shell test of concentric.py:164,211 reads values well above the
+// floor.  The input is first scaled by the power of two that brings max|a_ij| into [1, 2) and sigma
+// is scaled back at the end: the result is exactly scale invariant, svd(2^k A) = 2^k svd(A) bit for
+// bit, and neither ||A||_F^2 nor the rotation test (tol sqrt(al) sqrt(be)) overflows or underflows to
+// zero however large or small the entries are.
 //
 // Layout: the working arrays hold columns as contiguous ROWS (Gt: NP x m, Vw: NP x NP), in
 // the same physically-permuted round-robin order as eigh.hip, so a pivot pair is two
@@ -48,6 +55,28 @@ __device__ __forceinline__ double group16_sum(double v) {
     return v;
 }
 
+// max over the block (all threads get it); red: >= 17 doubles of LDS
+__device__ __forceinline__ double block_max(double v, double* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t = fmax(t, red[w]);
+        red[16] = t;
+    }
+    __syncthreads();
+    return red[16];
+}
+
+// the exponent e with max|a_ij| * 2^-e in [1, 2): the sweeps run on A 2^-e, sigma is scaled by 2^e after
+__device__ __forceinline__ int scale_exponent(double amax) {
+    return (amax > 0.0 && isfinite(amax)) ? ilogb(amax) : 0;
+}
+
 __global__ __launch_bounds__(SVD_THREADS) void svd_lds_kernel(const double* __restrict__ a, int M, int N, int NP,
                                                               int steps, double2* __restrict__ rot,
                                                               int* __restrict__ any_flags, int* __restrict__ nsteps_out,
@@ -62,10 +91,18 @@ __global__ __launch_bounds__(SVD_THREADS) void svd_lds_kernel(const double* __re
     const int grp = tid >> 4, gl = tid & 15;             // 64 groups of 16 lanes: one pair each
     const int mp = NP / 2, R = NP - 1;
 
-    double fro = 0.0;
+    double amax = 0.0;
     for (int idx = tid; idx < NP * M; idx += SVD_THREADS) {
         const int i = idx / NP, j = idx - i * NP;        // consecutive threads: consecutive columns of a row of A
         const double v = (j < N) ? a[(int64_t)i * N + j] : 0.0;
+        Gt[(size_t)j * M + i] = v;
+        amax = fmax(amax, fabs(v));
+    }
+    const int sexp = scale_exponent(block_max(amax, red));
+    double fro = 0.0;
+    for (int idx = tid; idx < NP * M; idx += SVD_THREADS) {  // the same elements this thread wrote
+        const int i = idx / NP, j = idx - i * NP;
+        const double v = ldexp(Gt[(size_t)j * M + i], -sexp);
         Gt[(size_t)j * M + i] = v;
         fro = fma(v, v, fro);
     }
@@ -108,7 +145,7 @@ __global__ __launch_bounds__(SVD_THREADS) void svd_lds_kernel(const double* __re
                 be = group16_sum(be);
                 ga = group16_sum(ga);
                 double c = 1.0, sn = 0.0;
-                const bool rotate = fabs(ga) > tol * sqrt(al * be) && al > floor2 && be > floor2;
+                const bool rotate = fabs(ga) > tol * sqrt(al) * sqrt(be) && al > floor2 && be > floor2;
                 if (rotate) {
                     const double zeta = (be - al) / (2.0 * ga);
                     const double az = fabs(zeta);
@@ -158,7 +195,7 @@ __global__ __launch_bounds__(SVD_THREADS) void svd_lds_kernel(const double* __re
         }
         rank_out[i] = rk;
         const int nsv = M < N ? M : N;
-        if (rk < nsv) s_out[rk] = si;
+        if (rk < nsv) s_out[rk] = ldexp(si, sexp);
     }
     if (tid == 0) {
         nsteps_out[0] = sweep * steps;
@@ -209,10 +246,17 @@ __global__ __launch_bounds__(SVD_THREADS) void svd_jacobi_kernel(const double* _
     const int wave = tid >> 6;
 
     // Gt[j][i] = A[i][j]; Vw = I; ||A||_F^2
-    double fro = 0.0;
+    double amax = 0.0;
     for (int64_t idx = tid; idx < (int64_t)NP * M; idx += SVD_THREADS) {
         const int j = (int)(idx / M), i = (int)(idx - (int64_t)j * M);
         const double v = (j < N) ? a[(int64_t)i * N + j] : 0.0;
+        G0[idx] = v;
+        amax = fmax(amax, fabs(v));
+    }
+    const int sexp = scale_exponent(block_max(amax, red));
+    double fro = 0.0;
+    for (int64_t idx = tid; idx < (int64_t)NP * M; idx += SVD_THREADS) {  // the same elements this thread wrote
+        const double v = ldexp(G0[idx], -sexp);
         G0[idx] = v;
         fro = fma(v, v, fro);
     }
@@ -255,7 +299,7 @@ __global__ __launch_bounds__(SVD_THREADS) void svd_jacobi_kernel(const double* _
                 be = nbx_wave_sum(be);
                 ga = nbx_wave_sum(ga);
                 double c = 1.0, s = 0.0;
-                const bool rotate = fabs(ga) > tol * sqrt(al * be) && al > floor2 && be > floor2;
+                const bool rotate = fabs(ga) > tol * sqrt(al) * sqrt(be) && al > floor2 && be > floor2;
                 if (rotate) {
                     const double zeta = (be - al) / (2.0 * ga);
                     const double az = fabs(zeta);
@@ -318,7 +362,7 @@ __global__ __launch_bounds__(SVD_THREADS) void svd_jacobi_kernel(const double* _
         }
         rank[i] = rk;
         const int nsv = M < N ? M : N;
-        if (rk < nsv) s_out[rk] = si;
+        if (rk < nsv) s_out[rk] = ldexp(si, sexp);
     }
     __syncthreads();
     for (int64_t idx = tid; idx < (int64_t)NP * N; idx += SVD_THREADS) {
