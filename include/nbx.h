@@ -107,6 +107,7 @@ int nbx_df_synth(nbx_ctx* ctx, int64_t nao, int64_t l0, int64_t l1, uint64_t see
 #define NBX_PROF_EIGH 3        /* eigh_jacobi_kernel                                         */
 #define NBX_PROF_SVD 4         /* svd_jacobi_kernel                                          */
 #define NBX_PROF_GEMM 5        /* every gemm_f64_kernel launch                               */
+#define NBX_PROF_LOC 6         /* loc_pm_kernel / loc_boys_kernel                            */
 /* on = 0: off; on = 1: every slot; on = 2 | (mask << 2): only the slots whose bit is set in
  * mask (an event pair costs a few microseconds of stream time, which matters inside an SCF
  * cycle: bench.py brackets the J/K kernel only).                                             */
@@ -442,6 +443,30 @@ int nbx_ao2mo_pair_sym(nbx_ctx* ctx, int64_t nao, const double* d_eri, const dou
  * sweep limit was hit. */
 int nbx_svd_status(nbx_ctx* ctx, int64_t m, int64_t n, const void* d_work, int* h_sweeps);
 
+/* ------------------------------------------------------------------ Localisation (Pipek-Mezey, Boys)
+ * Replaces pyscf.lo.PipekMezey(mol, C).kernel() and pyscf.lo.boys.Boys(mol, C).kernel() at
+ * nbed/localizers/occupied/pyscf.py:317-324,378-379: the orthogonal U (n x n) that maximises
+ * f(U) = sum_k sum_i ((U^T Q_k U)_ii)^2 by Jacobi sweeps; C_loc = C U.  One workgroup per problem, every sweep in
+ * one launch (csrc/localize.hip).
+ *   nbx_loc_pm    Q_A = 1/2 (X_A^T Y_A + Y_A^T X_A) over the AO rows [h_ao_offsets[A], h_ao_offsets[A+1]) of each
+ *                 atom; d_x, d_y (batch, nao, n) row-major, d_y NULL: Y = X.  h_ao_offsets: natm + 1 host values
+ *                 ascending from 0 to nao.  Copies them to the workspace (synchronises).
+ *   nbx_loc_boys  d_q (batch, 3, n, n) symmetric: C^T r_k C, k = x, y, z.
+ * d_u (batch, n, n).  The sweeps stop once a whole sweep's largest |sin gamma| is below tol, or after max_sweeps
+ * (d_u is written either way).  d_work: nbx_loc_worksize(kind, ...) bytes, kind NBX_LOC_PM or NBX_LOC_BOYS (Boys
+ * ignores nao and natm); too small: NBX_E_INVALID.  Identical inputs give bit-identical outputs.
+ * nbx_loc_status (synchronises) returns the sweeps and f of each problem of the last call on the workspace, and
+ * NBX_E_NOCONV if any problem hit max_sweeps.                                                        */
+#define NBX_LOC_PM 0
+#define NBX_LOC_BOYS 1
+size_t nbx_loc_worksize(int kind, int batch, int64_t nao, int64_t n, int64_t natm);
+int nbx_loc_pm(nbx_ctx* ctx, int batch, int64_t nao, int64_t n, int64_t natm, const int64_t* h_ao_offsets,
+               const double* d_x, const double* d_y, double* d_u, int max_sweeps, double tol, void* d_work,
+               size_t work_bytes);
+int nbx_loc_boys(nbx_ctx* ctx, int batch, int64_t n, const double* d_q, double* d_u, int max_sweeps, double tol,
+                 void* d_work, size_t work_bytes);
+int nbx_loc_status(nbx_ctx* ctx, int batch, const void* d_work, int* h_sweeps, double* h_f);
+
 /* ------------------------------------------------------------------ four-index transform
  * Replaces pyscf.ao2mo.kernel + ao2mo.restore(1, ...) at nbed/ham_builder.py:127-131:
  *   out[i-i0,j,k,l] = sum_pqrs C1[p,i] C2[q,j] C3[r,k] C4[s,l] (pq|rs),  i in [i0,i1)
@@ -709,6 +734,11 @@ int nbx_host_eri(int nshell, const int* ang, const int* nprim, const int* nfunc,
 int nbx_host_1e(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
                 const double* exps, const double* coefs, const double* sph, int natm, const double* charges,
                 const double* atom_xyz, int nthreads, double* s_out, double* t_out, double* v_out);
+/* Dipole matrices <mu| r |nu> (3, nao, nao) of the same shells, origin at 0, HOST memory: intor_symmetric("int1e_r",
+ * comp=3) behind pyscf.lo.boys (nbed/localizers/occupied/pyscf.py:378).  <a|x|b> = (E_1 + P_x E_0) (pi/p)^1/2 times
+ * the y and z overlap factors.                                                                        */
+int nbx_host_dipole(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                    const double* exps, const double* coefs, const double* sph, int nthreads, double* r_out);
 
 #ifdef __cplusplus
 }

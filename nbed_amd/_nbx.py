@@ -22,6 +22,7 @@ NBX_E_HIP = -2
 NBX_E_NOMEM = -3
 NBX_E_NOCONV = -4
 NBX_E_UNSUPPORTED = -5
+LOC_PM, LOC_BOYS = 0, 1  # nbx_loc_worksize kinds (NBX_LOC_PM, NBX_LOC_BOYS)
 
 HUZ_JK_PACKED, HUZ_JK_SYM = 0, 1
 XC_CODES = {"slater": 0, "lda": 1, "lda,vwn_rpa": 1, "lda,vwn": 2, "lda,vwn5": 2, "svwn": 2, "b3lyp": 3}
@@ -136,6 +137,10 @@ SIGNATURES = {
     "nbx_svd_worksize": (c_size_t, [c_int64, c_int64]),
     "nbx_svd_right": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, c_size_t]),
     "nbx_svd_status": (c_int, [_P, c_int64, c_int64, _P, POINTER(c_int)]),
+    "nbx_loc_worksize": (c_size_t, [c_int, c_int, c_int64, c_int64, c_int64]),
+    "nbx_loc_pm": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_int, c_double, _P, c_size_t]),
+    "nbx_loc_boys": (c_int, [_P, c_int, c_int64, _P, _P, c_int, c_double, _P, c_size_t]),
+    "nbx_loc_status": (c_int, [_P, c_int, _P, POINTER(c_int), POINTER(c_double)]),
     "nbx_ao2mo_worksize": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "nbx_ao2mo": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P,
                           c_int64, _P, _P, c_size_t]),
@@ -172,6 +177,7 @@ SIGNATURES = {
     "nbx_purify": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, _P, c_size_t, c_int, _P]),
     "nbx_host_1e": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, _P]),
     "nbx_host_eri": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_double, c_int, _P]),
+    "nbx_host_dipole": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "nbx_huz_cycle": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                               c_int, _P, _P]),
     "nbx_huz_cycle_jk": (c_int, [_P, POINTER(HuzState), _P]),

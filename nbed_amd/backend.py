@@ -1200,6 +1200,36 @@ class HipBackend:
             self.last_svd_sweeps = sweeps[0]
         return s, vt
 
+    # ------------------------------------------------------------------ orbital localisation (Jacobi sweeps)
+    def localize_pm(self, x, y, ao_offsets, max_sweeps: int = 1000, tol: float = 1e-10):
+        """Pipek-Mezey rotation of each problem of a batch (nbx_loc_pm): ``x``, ``y`` (batch, nao, n) device arrays
+        (``y`` None: Y = X), ``ao_offsets`` the natm + 1 AO offsets of the atoms.  Returns (U (batch, n, n) device,
+        sweeps, f) with C_loc = C U; raises NbxError when a problem hits ``max_sweeps``."""
+        batch, nao, n = (int(v) for v in x.shape)
+        offs = np.ascontiguousarray(ao_offsets, dtype=np.int64)
+        natm = int(offs.size) - 1
+        work = self._workspace("loc", int(self.lib.nbx_loc_worksize(_nbx.LOC_PM, batch, nao, n, natm)))
+        u = self.empty((batch, n, n))
+        self._call("nbx_loc_pm", batch, nao, n, natm, offs.ctypes.data_as(ctypes.c_void_p), self._p(x), self._p(y),
+                   self._p(u), int(max_sweeps), float(tol), self._p(work), work.numel())
+        return (u,) + self._loc_status(batch, work)
+
+    def localize_boys(self, q, max_sweeps: int = 1000, tol: float = 1e-10):
+        """Boys rotation of each problem of a batch (nbx_loc_boys): ``q`` (batch, 3, n, n) device array of the dipole
+        matrices C^T r_k C.  Returns (U (batch, n, n) device, sweeps, f); raises NbxError on the sweep limit."""
+        batch, n = int(q.shape[0]), int(q.shape[-1])
+        work = self._workspace("loc", int(self.lib.nbx_loc_worksize(_nbx.LOC_BOYS, batch, 0, n, 0)))
+        u = self.empty((batch, n, n))
+        self._call("nbx_loc_boys", batch, n, self._p(q), self._p(u), int(max_sweeps), float(tol), self._p(work),
+                   work.numel())
+        return (u,) + self._loc_status(batch, work)
+
+    def _loc_status(self, batch: int, work):
+        sweeps, f = (c_int * max(batch, 1))(), (c_double * max(batch, 1))()
+        self._call("nbx_loc_status", batch, self._p(work), sweeps, f)
+        self.last_loc_sweeps = list(sweeps[:batch])
+        return np.array(sweeps[:batch], dtype=np.int64), np.array(f[:batch], dtype=np.float64)
+
     # ------------------------------------------------------------------ four-index transform
     def ao2mo(self, eri, c1, c2, c3, c4, i0: int = 0, i1: int | None = None, out=None):
         """(i1-i0, n2, n3, n4) chemist-order MO integrals (nbx_ao2mo)."""

@@ -595,3 +595,88 @@ extern "C" int nbx_host_1e(int nshell, const int* ang, const int* nprim, const i
     for (auto& th : pool) th.join();
     return NBX_OK;
 }
+
+// Dipole matrices <a| r |b>, origin 0 (intor_symmetric("int1e_r", comp=3), what pyscf.lo.boys asks of the molecule):
+// per direction the one-dimensional factor of x = x_P + P_x over the Hermite expansion, (E_1 + P_x E_0) (pi/p)^1/2.
+extern "C" int nbx_host_dipole(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                               const double* exps, const double* coefs, const double* sph, int nthreads,
+                               double* r_out) {
+    if (nshell <= 0 || !ang || !nprim || !nfunc || !centres || !exps || !coefs || !sph || !r_out) return NBX_E_INVALID;
+    std::vector<Shell> shells(nshell);
+    int poff = 0, soff = 0, ao = 0;
+    for (int s = 0; s < nshell; ++s) {
+        if (ang[s] < 0 || ang[s] > LMAX || nprim[s] <= 0) return NBX_E_INVALID;
+        Shell& sh = shells[s];
+        sh.l = ang[s];
+        sh.nprim = nprim[s];
+        sh.ncart_ = ncart(sh.l);
+        sh.nsph = nfunc[s];
+        if (sh.nsph != 2 * sh.l + 1 && sh.nsph != sh.ncart_) return NBX_E_INVALID;
+        sh.exps = exps + poff;
+        sh.coefs = coefs + poff;
+        sh.sph = sph + soff;
+        sh.ao0 = ao;
+        for (int d = 0; d < 3; ++d) sh.c[d] = centres[3 * s + d];
+        poff += sh.nprim;
+        soff += sh.nsph * sh.ncart_;
+        ao += sh.nsph;
+    }
+    const int n = ao;
+    const size_t nn = size_t(n) * n;
+    const int64_t npair = int64_t(nshell) * (nshell + 1) / 2;
+    if (nthreads <= 0) nthreads = int(std::thread::hardware_concurrency());
+    if (nthreads <= 0) nthreads = 1;
+    std::atomic<int64_t> next{0};
+    auto body = [&] {
+        double br[3][100], orr[3][100];
+        for (;;) {
+            const int64_t ij = next.fetch_add(1);
+            if (ij >= npair) break;
+            int ia = int((std::sqrt(8.0 * double(ij) + 1.0) - 1.0) / 2.0);
+            while (int64_t(ia) * (ia + 1) / 2 > ij) --ia;
+            while (int64_t(ia + 1) * (ia + 2) / 2 <= ij) ++ia;
+            const int ib = int(ij - int64_t(ia) * (ia + 1) / 2);
+            const Shell &sa = shells[ia], &sb = shells[ib];
+            int ca[10][3], cb[10][3];
+            cart_list(sa.l, ca);
+            cart_list(sb.l, cb);
+            const int na = sa.ncart_, nb = sb.ncart_;
+            for (int d = 0; d < 3; ++d)
+                for (int k = 0; k < na * nb; ++k) br[d][k] = 0.0;
+            double ab[3];
+            for (int d = 0; d < 3; ++d) ab[d] = sa.c[d] - sb.c[d];
+            for (int i = 0; i < sa.nprim; ++i)
+                for (int j = 0; j < sb.nprim; ++j) {
+                    const double a = sa.exps[i], b = sb.exps[j], p = a + b, w = sa.coefs[i] * sb.coefs[j];
+                    double e[3][LMAX + 1][LB2 + 1][LMAX + LB2 + 1];
+                    for (int d = 0; d < 3; ++d) hermite_e_wide(sa.l, sb.l, a, b, ab[d], e[d]);
+                    const double pref = std::pow(M_PI / p, 1.5) * w;
+                    const double pc[3] = {(a * sa.c[0] + b * sb.c[0]) / p, (a * sa.c[1] + b * sb.c[1]) / p,
+                                          (a * sa.c[2] + b * sb.c[2]) / p};
+                    for (int x = 0; x < na; ++x)
+                        for (int y = 0; y < nb; ++y) {
+                            double s1[3], r1[3];
+                            for (int d = 0; d < 3; ++d) {
+                                const double* ed = e[d][ca[x][d]][cb[y][d]];
+                                s1[d] = ed[0];
+                                r1[d] = ed[1] + pc[d] * ed[0];
+                            }
+                            br[0][x * nb + y] += pref * r1[0] * s1[1] * s1[2];
+                            br[1][x * nb + y] += pref * s1[0] * r1[1] * s1[2];
+                            br[2][x * nb + y] += pref * s1[0] * s1[1] * r1[2];
+                        }
+                }
+            for (int d = 0; d < 3; ++d) block_to_ao(sa, sb, br[d], orr[d]);
+            for (int m = 0; m < sa.nsph; ++m)
+                for (int k = 0; k < sb.nsph; ++k) {
+                    const size_t r = size_t(sa.ao0 + m), c = size_t(sb.ao0 + k);
+                    for (int d = 0; d < 3; ++d) r_out[d * nn + r * n + c] = r_out[d * nn + c * n + r] = orr[d][m * sb.nsph + k];
+                }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nthreads; ++t) pool.emplace_back(body);
+    body();
+    for (auto& th : pool) th.join();
+    return NBX_OK;
+}

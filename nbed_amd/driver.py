@@ -38,7 +38,8 @@ from .config import NbedConfig, OccupiedLocalizerTypes, ProjectorTypes, VirtualL
 from .exceptions import NbedDriverError
 from .ham_builder import HamiltonianBuilder
 from .localizers import ConcentricLocalizer, LocalizedSystem, SPADELocalizer
-from .localizers.occupied.unsupported import BOYSLocalizer, IBOLocalizer, PMLocalizer
+from .localizers.occupied.jacobi import BOYSLocalizer, PMLocalizer
+from .localizers.occupied.unsupported import IBOLocalizer
 from .scf import energy_elec
 from .scf.huzinaga_scf import huzinaga_scf
 
@@ -196,7 +197,16 @@ class BuiltinHFProvider:
             raise NbedDriverError(f"{nelectron} electrons are incompatible with spin {spin}")
         nelec = ((nelectron + spin) // 2, (nelectron - spin) // 2)
         return Mole(ints["nao"], nelec, ao_slices=ints["ao_slices"], e_nuc=ints["e_nuc"], atom=config.geometry,
-                    basis=config.basis, charge=config.charge)
+                    basis=config.basis, charge=config.charge, dipole=lambda: self._dipole(config))
+
+    def _dipole(self, config: NbedConfig):
+        """The (3, nao, nao) dipole matrices of the molecule (Boys localisation), computed on first use."""
+        from . import integrals
+
+        key = ("dipole", config.geometry, str(config.basis).lower(), str(config.unit))
+        if key not in self._cache:
+            self._cache[key] = integrals.molecule_dipole(config.geometry, str(config.basis), str(config.unit))
+        return self._cache[key]
 
     def global_hf(self, config: NbedConfig):
         """Converged global UHF (nbed/driver.py:106-124), on libnbx."""
@@ -407,11 +417,15 @@ class NbedDriver:
                                            max_shells=self.config.max_shells, n_mo_overwrite=self.n_mo_overwrite,
                                            backend=self.be)
             case OccupiedLocalizerTypes.BOYS:
-                localizer = BOYSLocalizer(self._global_ks, self.config.n_active_atoms)
+                localizer = BOYSLocalizer(self._global_ks, self.config.n_active_atoms,
+                                          occ_cutoff=self.config.occupied_threshold,
+                                          virt_cutoff=self.config.virtual_threshold, backend=self.be)
             case OccupiedLocalizerTypes.IBO:
                 localizer = IBOLocalizer(self._global_ks, self.config.n_active_atoms)
             case OccupiedLocalizerTypes.PM:
-                localizer = PMLocalizer(self._global_ks, self.config.n_active_atoms)
+                localizer = PMLocalizer(self._global_ks, self.config.n_active_atoms,
+                                        occ_cutoff=self.config.occupied_threshold,
+                                        virt_cutoff=self.config.virtual_threshold, backend=self.be)
         self.localizer = localizer
         return localizer.localize()
 

@@ -378,6 +378,27 @@ def one_electron(basis: Basis):
     return basis.to_ao(s_mat), basis.to_ao(t_mat), basis.to_ao(v_mat)
 
 
+def dipole(basis: Basis) -> np.ndarray:
+    """(3, nao, nao) dipole matrices <a| r |b>, origin at 0: PySCF's ``mol.intor_symmetric("int1e_r", comp=3)``,
+    which ``pyscf.lo.boys`` asks for (nbed/localizers/occupied/pyscf.py:378).  Per direction the one-dimensional
+    factor is (E_1 + P_x E_0) (pi/p)^1/2: x = (x - P_x) + P_x over the Hermite expansion about P."""
+    n = basis.nao_cart
+    out = np.zeros((3, n, n))
+    for (ish, sa), (jsh, sb) in itertools.product(enumerate(basis.shells), repeat=2):
+        pr = _Pair(sa, sb)
+        pref = (math.pi / pr.p) ** 1.5
+        for ia, la in enumerate(sa.cart):
+            for ib, lb in enumerate(sb.cart):
+                w = pr.weights(ia, ib)
+                s1 = [pr.e[d][(la[d], lb[d], 0)] for d in range(3)]
+                r1 = [pr.e[d].get((la[d], lb[d], 1), 0.0) + pr.centre[:, d] * s1[d] for d in range(3)]
+                i, j = basis.shell_ao0[ish] + ia, basis.shell_ao0[jsh] + ib
+                for d in range(3):
+                    f = [r1[k] if k == d else s1[k] for k in range(3)]
+                    out[d, i, j] = np.dot(w, f[0] * f[1] * f[2] * pref)
+    return np.stack([basis.to_ao(out[d]) for d in range(3)])
+
+
 def overlap_cross(basis_a: Basis, basis_b: Basis) -> np.ndarray:
     """<a_i | b_j> between the AOs of two basis sets (possibly of different molecules / kinds):
     PySCF's ``gto.intor_cross('int1e_ovlp_sph', mol_a, mol_b)`` (nbed/localizers/virtual/concentric.py:83-88)."""
@@ -462,6 +483,28 @@ def one_electron_native(basis: Basis, nthreads: int = 0):
     _nbx.check(lib, lib.nbx_host_1e(len(basis.shells), ptr(ang), ptr(nprim), ptr(nfunc), ptr(centres), ptr(exps), ptr(coefs),
                                     ptr(sph), len(charges), ptr(charges), ptr(xyz), int(nthreads), *(ptr(o) for o in out)))
     return tuple(out)
+
+
+def dipole_native(basis: Basis, nthreads: int = 0) -> np.ndarray:
+    """(3, nao, nao) dipole matrices from libnbx's host engine (``nbx_host_dipole``): ``dipole`` in threaded C++."""
+    import ctypes
+
+    from . import _nbx
+
+    lib = _nbx.load_library()
+    ang, nprim, nfunc, centres, exps, coefs, sph = _shell_arrays(basis)
+    out = np.empty((3, basis.nao, basis.nao))
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    _nbx.check(lib, lib.nbx_host_dipole(len(basis.shells), ptr(ang), ptr(nprim), ptr(nfunc), ptr(centres), ptr(exps),
+                                        ptr(coefs), ptr(sph), int(nthreads), ptr(out)))
+    return out
+
+
+def molecule_dipole(xyz: str, basis: str = "sto-3g", unit: str = "angstrom", cart: bool = False,
+                    engine: str = "native") -> np.ndarray:
+    """The dipole matrices of a molecule, on the same shells as ``molecule_integrals``."""
+    bs = Basis(parse_geometry(xyz, unit), basis, cart)
+    return dipole_native(bs) if engine == "native" else dipole(bs)
 
 
 def two_electron_native(basis: Basis, nthreads: int = 0, cutoff: float = 1e-16) -> np.ndarray:

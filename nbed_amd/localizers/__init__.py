@@ -3,7 +3,8 @@
 from .ace import ACELocalizer
 from .occupied.base import OccupiedLocalizer
 from .occupied.spade import SPADELocalizer
-from .occupied.unsupported import BOYSLocalizer, IBOLocalizer, PMLocalizer
+from .occupied.jacobi import BOYSLocalizer, PMLocalizer
+from .occupied.unsupported import IBOLocalizer
 from .system import LocalizedSystem
 from .virtual.base import VirtualLocalizer
 from .virtual.concentric import ConcentricLocalizer

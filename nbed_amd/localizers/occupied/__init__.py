@@ -2,6 +2,7 @@
 
 from .base import OccupiedLocalizer
 from .spade import SPADELocalizer
-from .unsupported import BOYSLocalizer, IBOLocalizer, PMLocalizer
+from .jacobi import BOYSLocalizer, PMLocalizer
+from .unsupported import IBOLocalizer
 
 __all__ = ["BOYSLocalizer", "IBOLocalizer", "PMLocalizer", "SPADELocalizer", "OccupiedLocalizer"]

@@ -1,9 +1,8 @@
-"""Names the reference exports whose algorithms are outside the hot path.
+"""Names the reference exports whose algorithms are not built here.
 
-PM / Boys / IBO localisation are iterative Jacobi-sweep schemes inside PySCF's ``lo`` module
-(nbed/localizers/occupied/pyscf.py); no configuration of BASELINE.json uses them
-(component 8).  The classes stay importable so that code written
-against ``nbed.localizers`` loads, and fail loudly when instantiated.
+IBO localisation (nbed/localizers/occupied/pyscf.py:382-438) needs intrinsic atomic orbitals built on PySCF's
+MINAO basis data.  The class stays importable so that code written against ``nbed.localizers`` loads, and fails
+loudly when instantiated.  Pipek-Mezey and Boys are in ``jacobi.py``.
 """
 
 from __future__ import annotations
@@ -16,20 +15,12 @@ class _Unsupported(OccupiedLocalizer):
 
     def __init__(self, *args, **kwargs):
         raise NotImplementedError(
-            f"{self._name} localisation is not part of the MI355X hot path (SPADE is); "
-            "use localization='spade'."
+            f"{self._name} localisation is not part of the MI355X hot path (SPADE, PM and Boys are); "
+            "use localization='spade', 'pm' or 'boys'."
         )
 
     def _localize_spin(self, c_matrix, occupancy, n_mo_overwrite=None):  # pragma: no cover
         raise NotImplementedError
-
-
-class PMLocalizer(_Unsupported):
-    _name = "Pipek-Mezey"
-
-
-class BOYSLocalizer(_Unsupported):
-    _name = "Boys"
 
 
 class IBOLocalizer(_Unsupported):

@@ -37,13 +37,16 @@ class _TrackedCycleRejected(RuntimeError):
 class Mole:
     """The ``gto.Mole`` attributes the path reads."""
 
-    def __init__(self, nao, nelec, ao_slices=None, e_nuc=0.0, atom=None, basis=None, charge=0):
+    def __init__(self, nao, nelec, ao_slices=None, e_nuc=0.0, atom=None, basis=None, charge=0, dipole=None):
+        """``dipole``: a callable returning the (3, nao, nao) dipole matrices of the geometry, unit and basis of the
+        overlap this molecule goes with (called on first use: only Boys localisation asks for them)."""
         self.nao = int(nao)
         self.atom = atom
         self.basis = basis
         self.charge = charge
         self._ao_slices = ao_slices
         self._e_nuc = float(e_nuc)
+        self._dipole = dipole
         self.nelec = (int(nelec[0]), int(nelec[1]))
 
     @property
@@ -67,6 +70,21 @@ class Mole:
 
     def energy_nuc(self):
         return self._e_nuc
+
+    def intor(self, intor, comp=None, **kwargs):
+        """``gto.Mole.intor`` for the one integral the path asks a molecule for: "int1e_r" (origin 0)."""
+        name = str(intor)
+        for suffix in ("_sph", "_cart"):
+            name = name.removesuffix(suffix)
+        if name != "int1e_r":
+            raise NotImplementedError(f"the built-in molecule has no integral {intor!r} (only 'int1e_r')")
+        if self._dipole is None:
+            raise NotImplementedError("this molecule has no source of dipole integrals (int1e_r): it comes from "
+                                      "neither PySCF nor the built-in integral provider")
+        return np.array(self._dipole(), dtype=np.float64)
+
+    def intor_symmetric(self, intor, comp=None, **kwargs):
+        return self.intor(intor, comp, **kwargs)
 
 
 # Below this many basis functions the packed J/K kernel has no edge over the symmetric one (both
