@@ -175,8 +175,9 @@ __device__ __forceinline__ void xc_vwn(double s, double ra, double rb, XcDer& o)
     const double zeta = (ra - rb) / rho;
     const double x = sqrt(cbrt(0.238732414637843 / rho));  // sqrt(rs), rs = (3 / (4 pi rho))^(1/3)
     const double c43 = 0.5198420997897464;                   // 2^(4/3) - 2
-    const double cp = cbrt(1.0 + zeta), cm = cbrt(1.0 - zeta);
-    const double fz = (cp * (1.0 + zeta) + cm * (1.0 - zeta) - 2.0) / c43;
+    const double up = 2.0 * ra / rho, dn = 2.0 * rb / rho;  // 1 +- zeta, never by subtraction: zeta -> +-1 when a spin is empty
+    const double cp = cbrt(up), cm = cbrt(dn);
+    const double fz = (cp * up + cm * dn - 2.0) / c43;
     const double dfz = (4.0 / 3.0) * (cp - cm) / c43;
     double ep, dep, ef, def, eps, dx, dz;
     if (RPA) {
@@ -192,15 +193,16 @@ __device__ __forceinline__ void xc_vwn(double s, double ra, double rb, XcDer& o)
         xc_vwn_fit(x, -0.01688686394038963, -0.0047584, 1.13107, 13.0045, al, dal);  // -1 / (6 pi^2): spin stiffness
         const double fpp0 = 1.7099209341613653;  // 4 / (9 (2^(1/3) - 1))
         const double z3 = zeta * zeta * zeta, z4 = z3 * zeta;
-        eps = ep + al * fz / fpp0 * (1.0 - z4) + (ef - ep) * fz * z4;
-        dx = dep + dal * fz / fpp0 * (1.0 - z4) + (def - dep) * fz * z4;
-        dz = al / fpp0 * (dfz * (1.0 - z4) - 4.0 * fz * z3) + (ef - ep) * (dfz * z4 + 4.0 * fz * z3);
+        const double omz4 = up * dn * fma(zeta, zeta, 1.0);  // 1 - zeta^4 as a product of its factors
+        eps = ep + al * fz / fpp0 * omz4 + (ef - ep) * fz * z4;
+        dx = dep + dal * fz / fpp0 * omz4 + (def - dep) * fz * z4;
+        dz = al / fpp0 * (dfz * omz4 - 4.0 * fz * z3) + (ef - ep) * (dfz * z4 + 4.0 * fz * z3);
     }
     // e = rho eps(rs, zeta):  d/d rho_s = eps - (rs / 3) d eps / d rs  +-  (1 -+ zeta) d eps / d zeta,  d/d rs = (d/dx) / (2 x)
     const double common = eps - (x / 6.0) * dx;
     o.e += s * rho * eps;
-    o.va += s * (common + (1.0 - zeta) * dz);
-    o.vb += s * (common - (1.0 + zeta) * dz);
+    o.va += s * (common + dn * dz);
+    o.vb += s * (common - up * dz);
 }
 
 // Lee-Yang-Parr in the gradient-only form of Miehlich, Savin, Stoll and Preuss (CPL 157, 200 (1989)):
@@ -223,7 +225,9 @@ __device__ __forceinline__ void xc_lyp(double s, double ra, double rb, double sa
     const double mix = (ra * saa + rb * sbb) / rho;
     const double P = k1 * (ra53 * ra + rb53 * rb) + (47.0 / 18.0 - 7.0 * delta / 18.0) * st - (2.5 - delta / 18.0) * (saa + sbb) -
                      (delta - 11.0) / 9.0 * mix;
-    const double Q = -2.0 / 3.0 * rho2 * st + (2.0 / 3.0 * rho2 - ra * ra) * sbb + (2.0 / 3.0 * rho2 - rb * rb) * saa;
+    // the paper's -2/3 rho^2 st + (2/3 rho^2 - ra^2) sbb + (2/3 rho^2 - rb^2) saa with the rho^2 sigma_ss terms, which
+    // cancel, taken out (they swamp what is left when one spin is nearly empty)
+    const double Q = -4.0 / 3.0 * rho2 * sab - ra * ra * sbb - rb * rb * saa;
     const double B = ra * rb * P + Q;
     const double ab = a * b;
     o.e += s * (-4.0 * a * ra * rb / (rho * den) - ab * omega * B);
@@ -234,13 +238,13 @@ __device__ __forceinline__ void xc_lyp(double s, double ra, double rb, double sa
     {   // d / d rho_a
         const double dt1 = -4.0 * a * (rb / (rho * den) - ra * rb / (rho2 * den) + ra * rb / rho * t1c);
         const double dP = k1 * (8.0 / 3.0) * ra53 + ddel * dPdd - (delta - 11.0) / 9.0 * (saa - mix) / rho;
-        const double dQ = -4.0 / 3.0 * rho * st + (4.0 / 3.0 * rho - 2.0 * ra) * sbb + 4.0 / 3.0 * rho * saa;
+        const double dQ = -8.0 / 3.0 * rho * sab - 2.0 * ra * sbb;
         o.va += s * (dt1 - ab * (dom * B + omega * (rb * P + ra * rb * dP + dQ)));
     }
     {   // d / d rho_b
         const double dt1 = -4.0 * a * (ra / (rho * den) - ra * rb / (rho2 * den) + ra * rb / rho * t1c);
         const double dP = k1 * (8.0 / 3.0) * rb53 + ddel * dPdd - (delta - 11.0) / 9.0 * (sbb - mix) / rho;
-        const double dQ = -4.0 / 3.0 * rho * st + (4.0 / 3.0 * rho - 2.0 * rb) * saa + 4.0 / 3.0 * rho * sbb;
+        const double dQ = -8.0 / 3.0 * rho * sab - 2.0 * rb * saa;
         o.vb += s * (dt1 - ab * (dom * B + omega * (ra * P + ra * rb * dP + dQ)));
     }
     const double abw = -ab * omega;

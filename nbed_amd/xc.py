@@ -343,7 +343,7 @@ def _b88_correction(t, ra, rb, saa, sbb):
 def _vwn_rpa(t, ra, rb):
     """Vosko-Wilk-Nusair correlation, the fit to the RPA data (libxc LDA_C_VWN_RPA; Gaussian's "VWN3")."""
     rho = ra + rb
-    zeta = (ra - rb) / rho
+    up, dn = 2.0 * ra / rho, 2.0 * rb / rho  # 1 +- zeta, never by subtraction: zeta -> +-1 when a spin is empty
     x = ((3.0 / (4.0 * math.pi)) / rho) ** (1.0 / 6.0)  # sqrt(rs)
 
     def ec(a, x0, b, c):
@@ -356,7 +356,7 @@ def _vwn_rpa(t, ra, rb):
 
     ec_p = ec(0.0310907, -0.409286, 13.0720, 42.7198)
     ec_f = ec(0.01554535, -0.743294, 20.1231, 101.578)
-    fz = ((1.0 + zeta) ** (4.0 / 3.0) + (1.0 - zeta) ** (4.0 / 3.0) - 2.0) / (2.0 ** (4.0 / 3.0) - 2.0)
+    fz = (up ** (4.0 / 3.0) + dn ** (4.0 / 3.0) - 2.0) / (2.0 ** (4.0 / 3.0) - 2.0)
     return rho * (ec_p + fz * (ec_f - ec_p))
 
 
@@ -365,6 +365,7 @@ def _vwn5(t, ra, rb):
     paper (libxc LDA_C_VWN, what PySCF means by "vwn" -- its default functional is "lda,vwn")."""
     rho = ra + rb
     zeta = (ra - rb) / rho
+    up, dn = 2.0 * ra / rho, 2.0 * rb / rho  # 1 +- zeta, never by subtraction: zeta -> +-1 when a spin is empty
     x = ((3.0 / (4.0 * math.pi)) / rho) ** (1.0 / 6.0)  # sqrt(rs)
 
     def ec(a, x0, b, c):
@@ -378,10 +379,11 @@ def _vwn5(t, ra, rb):
     ec_p = ec(0.0310907, -0.10498, 3.72744, 12.9352)
     ec_f = ec(0.01554535, -0.32500, 7.06042, 18.0578)
     alpha = ec(-1.0 / (6.0 * math.pi**2), -0.0047584, 1.13107, 13.0045)  # spin stiffness
-    fz = ((1.0 + zeta) ** (4.0 / 3.0) + (1.0 - zeta) ** (4.0 / 3.0) - 2.0) / (2.0 ** (4.0 / 3.0) - 2.0)
+    fz = (up ** (4.0 / 3.0) + dn ** (4.0 / 3.0) - 2.0) / (2.0 ** (4.0 / 3.0) - 2.0)
     fpp0 = 4.0 / (9.0 * (2.0 ** (1.0 / 3.0) - 1.0))
     z4 = zeta**4
-    return rho * (ec_p + alpha * fz / fpp0 * (1.0 - z4) + (ec_f - ec_p) * fz * z4)
+    omz4 = up * dn * (1.0 + zeta * zeta)  # 1 - zeta^4 as a product of its factors
+    return rho * (ec_p + alpha * fz / fpp0 * omz4 + (ec_f - ec_p) * fz * z4)
 
 
 def _lyp(t, ra, rb, saa, sab, sbb):
@@ -399,9 +401,9 @@ def _lyp(t, ra, rb, saa, sab, sbb):
                         + (47.0 / 18.0 - 7.0 * delta / 18.0) * stot
                         - (2.5 - delta / 18.0) * (saa + sbb)
                         - (delta - 11.0) / 9.0 * (ra / rho * saa + rb / rho * sbb))
-             - 2.0 / 3.0 * rho * rho * stot
-             + (2.0 / 3.0 * rho * rho - ra * ra) * sbb
-             + (2.0 / 3.0 * rho * rho - rb * rb) * saa)
+             # the paper's -2/3 rho^2 stot + (2/3 rho^2 - ra^2) sbb + (2/3 rho^2 - rb^2) saa with the rho^2 sigma_ss
+             # terms, which cancel, taken out (they swamp what is left when one spin is nearly empty)
+             - 4.0 / 3.0 * rho * rho * sab - ra * ra * sbb - rb * rb * saa)
     return t1 - a * b * omega * brace
 
 
