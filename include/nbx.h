@@ -740,6 +740,57 @@ int nbx_host_1e(int nshell, const int* ang, const int* nprim, const int* nfunc, 
 int nbx_host_dipole(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
                     const double* exps, const double* coefs, const double* sph, int nthreads, double* r_out);
 
+/* ------------------------------------------------------------------ coupled cluster (csrc/ccsd.hip)
+ * What surrounds the GEMMs of a spin-orbital CCSD (nbed_amd/ccsd_gpu.py): the reference runs PySCF's
+ * cc.CCSD on the embedded object (nbed/driver.py:1105-1135); here the amplitude equations of
+ * nbed_amd/ccsd.py run on the device with every contraction an nbx_gemm.  Spin orbital 2p + s has
+ * spatial orbital p and spin s (alpha = 0): the convention of nbx_spinorb_scatter.  None of these
+ * synchronises.
+ *
+ * Antisymmetrised block  out[a,b,c,d] = <P Q || R S>,  P = idx1[a], Q = idx2[b], R = idx3[c], S = idx4[d],
+ * of the Hamiltonian whose spatial blocks are d_two_body (3, n, n, n, n): aaaa, bbbb, aabb in physicist
+ * order, truncated and halved as build_spatial() leaves them (nbx_threshold_scale).  With h2 the
+ * spin-orbital tensor of build() -- h2[P,Q,R,S] is block aaaa / bbbb / aabb[p,q,r,s] / aabb[q,p,s,r] for
+ * the spins (a,a,a,a) / (b,b,b,b) / (a,b,b,a) / (b,a,a,b) and zero otherwise -- and w[P,Q,R,S] = 2 h2[P,Q,S,R],
+ *      <PQ||RS> = 0.5 ((w[P,Q,R,S] - w[P,Q,S,R]) - (w[Q,P,R,S] - w[Q,P,S,R])),
+ * the four terms of nbed_amd.ccsd.antisymmetrized in its order.  The (2n)^4 tensor is never formed.
+ *   pack_last  != 0: idx3 and idx4 are the same list and only c < d is written, as pair index
+ *                    c (2 n3 - c - 1) / 2 + (d - c - 1); pack_first: the same for a < b.
+ *   d_idx*         : device int arrays of spin-orbital indices in [0, 2n)                          */
+int nbx_ccsd_gather(nbx_ctx* ctx, int64_t n, const double* d_two_body, const int* d_idx1, int64_t n1,
+                    const int* d_idx2, int64_t n2, const int* d_idx3, int64_t n3, const int* d_idx4, int64_t n4,
+                    int pack_first, int pack_last, double* d_out);
+/* Fock matrix of the determinant that occupies the spin orbitals d_occ (nocc ints), over all 2n spin
+ * orbitals: f[P,Q] = h1[P,Q] + sum_I <P I || Q I>, d_h1 and d_fock (2n, 2n); the mean field the CCSD of
+ * nbed/driver.py:1105-1135 starts from, without a (2n)^4 tensor.                                  */
+int nbx_ccsd_fock(nbx_ctx* ctx, int64_t n, const double* d_two_body, const double* d_h1, const int* d_occ,
+                  int64_t nocc, double* d_fock);
+/* out = alpha * transpose(in, perm) + beta * out for a four-index tensor: h_extents (4) are the extents of
+ * `in`, output axis k is input axis h_perm[k] (numpy.transpose), any of the 24 permutations, any extents
+ * (lower ranks: leading extents of 1).  beta == 0: `out` is not read.  The permutes that turn a contraction
+ * of the CCSD equations (nbed/driver.py:1105-1135) into a matrix product, and with beta = 1 the P(ij),
+ * P(ab) antisymmetrisations of the doubles residual.  Tiled through LDS when the fastest axis changes.  */
+int nbx_permute4(nbx_ctx* ctx, const int64_t* h_extents, const int* h_perm, double alpha, const double* d_in,
+                 double beta, double* d_out);
+/* Antisymmetric index pairs of the CCSD tensors (nbed/driver.py:1105-1135): x (lead, n, n, trail) with
+ * x[l,e,f,t] = -x[l,f,e,t] against packed (lead, n(n-1)/2, trail) over e < f, pair index
+ * e (2n - e - 1) / 2 + (f - e - 1).  pack reads the e < f element; unpack writes
+ * x = alpha * (+packed | -packed | 0 on the diagonal) + beta * x  (beta == 0: x is not read).       */
+int nbx_pair_pack(nbx_ctx* ctx, int64_t lead, int64_t n, int64_t trail, const double* d_x, double* d_packed);
+int nbx_pair_unpack(nbx_ctx* ctx, int64_t lead, int64_t n, int64_t trail, double alpha, const double* d_packed,
+                    double beta, double* d_x);
+/* out[i,j,a,b] = c_t2 t2[i,j,a,b] + c_direct t1[i,a] t1[j,b] - c_exchange t1[i,b] t1[j,a]: tau (1, 1, 1),
+ * tau~ (1, 1/2, 1/2) and the 1/2 t2 + t1 t1 of W_mbej (1/2, 1, 0) of the CCSD equations
+ * (nbed/driver.py:1105-1135).  packed != 0: out is (nocc(nocc-1)/2, nvir(nvir-1)/2) over i < j, a < b.  */
+int nbx_ccsd_tau(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_t1, const double* d_t2, double c_t2,
+                 double c_direct, double c_exchange, int packed, double* d_out);
+/* Amplitude update of a CCSD cycle (nbed/driver.py:1105-1135) over the concatenated [t1 | t2] vector of
+ * nocc nvir + (nocc nvir)^2 doubles: t_new = r / D with D_ia = eo[i] - ev[a], D_ijab = eo[i] + eo[j] - ev[a]
+ * - ev[b] (the occupied / virtual Fock diagonals), err = t_new - t_old, and max |err| (NaN if any is) into the
+ * device double d_maxerr.  d_t_new and d_err are typically a slot of the DIIS history.              */
+int nbx_ccsd_update(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_r, const double* d_t_old,
+                    const double* d_eo, const double* d_ev, double* d_t_new, double* d_err, double* d_maxerr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,13 @@ SIGNATURES = {
     "nbx_mu_cycle_fock_post": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, c_int, _P, _P]),
     "nbx_huz_cycle_post": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                                    _P, _P]),
+    "nbx_ccsd_gather": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int, c_int, _P]),
+    "nbx_ccsd_fock": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P]),
+    "nbx_permute4": (c_int, [_P, POINTER(c_int64), POINTER(c_int), c_double, _P, c_double, _P]),
+    "nbx_pair_pack": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
+    "nbx_pair_unpack": (c_int, [_P, c_int64, c_int64, c_int64, c_double, _P, c_double, _P]),
+    "nbx_ccsd_tau": (c_int, [_P, c_int64, c_int64, _P, _P, c_double, c_double, c_double, c_int, _P]),
+    "nbx_ccsd_update": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

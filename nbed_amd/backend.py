@@ -1402,3 +1402,103 @@ class HipBackend:
         self._call("nbx_spinorb_scatter", n, self._p(one_body), self._p(two_body), tol, h2_scale, self._p(h1),
                    self._p(h2))
         return h1, h2
+
+    # ------------------------------------------------------------------ coupled cluster (csrc/ccsd.hip)
+    def index_array(self, idx, limit: int):
+        """Spin-orbital index list -> device int32 array (checked against ``limit`` here: the kernels trust it)."""
+        h = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        if h.size and (h.min() < 0 or h.max() >= limit):
+            raise ValueError(f"index list outside [0, {limit})")
+        return self.torch.from_numpy(h).to(self.device)
+
+    def ccsd_gather(self, two_body, i1, i2, i3, i4, pack_first: bool = False, pack_last: bool = False):
+        """<PQ||RS> for P in i1, Q in i2, R in i3, S in i4 (device index arrays of ``index_array``) from the (3, n, n, n, n)
+        spatial blocks; ``pack_last`` / ``pack_first``: the pair over R < S / P < Q (the two lists of a pair must be one)."""
+        n = two_body.shape[-1]
+        n1, n2, n3, n4 = (int(i.numel()) for i in (i1, i2, i3, i4))
+        if (pack_first and i1 is not i2) or (pack_last and i3 is not i4):
+            raise ValueError("a packed pair needs the same index list on both of its positions")
+        rows = (n1 * (n1 - 1) // 2,) if pack_first else (n1, n2)
+        cols = (n3 * (n3 - 1) // 2,) if pack_last else (n3, n4)
+        out = self.empty(rows + cols)
+        self._call("nbx_ccsd_gather", n, self._p(two_body), self._p(i1), n1, self._p(i2), n2, self._p(i3), n3, self._p(i4),
+                   n4, int(pack_first), int(pack_last), self._p(out))
+        return out
+
+    def ccsd_fock(self, two_body, h1, occ):
+        """f = h1 + sum_I <PI||QI> over the occupied spin orbitals ``occ`` (device index array), (2n, 2n)."""
+        n = two_body.shape[-1]
+        out = self.empty((2 * n, 2 * n))
+        self._call("nbx_ccsd_fock", n, self._p(two_body), self._p(h1), self._p(occ), int(occ.numel()), self._p(out))
+        return out
+
+    def permute4(self, x, perm, alpha: float = 1.0, beta: float = 0.0, out=None):
+        """alpha * x.transpose(perm) + beta * out, materialised; up to four axes."""
+        nd = x.dim()
+        if nd > 4 or sorted(perm) != list(range(nd)):
+            raise ValueError(f"permute4: bad permutation {perm} of {nd} axes")
+        ext = [1] * (4 - nd) + [int(s) for s in x.shape]
+        p4 = list(range(4 - nd)) + [int(p) + 4 - nd for p in perm]
+        shape = tuple(int(x.shape[p]) for p in perm)
+        if out is None:
+            if beta != 0.0:
+                raise ValueError("permute4: beta != 0 needs out")
+            out = self.empty(shape)
+        elif out.numel() != x.numel():
+            raise ValueError("permute4: out has another size")
+        self._call("nbx_permute4", (ctypes.c_int64 * 4)(*ext), (c_int * 4)(*p4), float(alpha), self._p(x), float(beta),
+                   self._p(out))
+        return out
+
+    def pair_pack(self, x, lead: int, n: int, trail: int):
+        """(lead, n, n, trail) -> (lead, n(n-1)/2, trail): the e < f elements."""
+        if x.numel() != lead * n * n * trail:
+            raise ValueError("pair_pack: shape")
+        out = self.empty((lead, n * (n - 1) // 2, trail))
+        self._call("nbx_pair_pack", lead, n, trail, self._p(x), self._p(out))
+        return out
+
+    def pair_unpack(self, packed, lead: int, n: int, trail: int, alpha: float = 1.0, beta: float = 0.0, out=None):
+        """The antisymmetric (lead, n, n, trail) tensor of a packed one: alpha * unpacked + beta * out."""
+        if packed.numel() != lead * (n * (n - 1) // 2) * trail:
+            raise ValueError("pair_unpack: shape")
+        if out is None:
+            if beta != 0.0:
+                raise ValueError("pair_unpack: beta != 0 needs out")
+            out = self.empty((lead, n, n, trail))
+        elif out.numel() != lead * n * n * trail:
+            raise ValueError("pair_unpack: out has another size")
+        self._call("nbx_pair_unpack", lead, n, trail, float(alpha), self._p(packed), float(beta), self._p(out))
+        return out
+
+    def ccsd_tau(self, t1, t2, c_t2: float, c_direct: float, c_exchange: float, packed: bool = False):
+        """c_t2 t2 + c_direct t1_ia t1_jb - c_exchange t1_ib t1_ja; ``packed``: over (i < j, a < b)."""
+        no, nv = int(t1.shape[0]), int(t1.shape[1])
+        out = self.empty((no * (no - 1) // 2, nv * (nv - 1) // 2)) if packed else self.empty((no, no, nv, nv))
+        self._call("nbx_ccsd_tau", no, nv, self._p(t1), self._p(t2), float(c_t2), float(c_direct), float(c_exchange),
+                   int(packed), self._p(out))
+        return out
+
+    def ccsd_update(self, no: int, nv: int, r, t_old, eo, ev, t_new, err, maxerr):
+        """t_new = r / D, err = t_new - t_old over the [t1 | t2] vector; max |err| into the device double ``maxerr``."""
+        nvec = no * nv + (no * nv) ** 2
+        for t in (r, t_old, t_new, err):
+            if t.numel() != nvec:
+                raise ValueError("ccsd_update: vector length")
+        self._call("nbx_ccsd_update", no, nv, self._p(r), self._p(t_old), self._p(eo), self._p(ev), self._p(t_new),
+                   self._p(err), self._p(maxerr))
+
+    def read_scalars(self, d) -> np.ndarray:
+        """A few device doubles -> host (synchronises)."""
+        out = (c_double * d.numel())()
+        self._call("nbx_memcpy_d2h", out, self._p(d), 8 * d.numel())
+        return np.array(out[:], dtype=np.float64)
+
+    def free_bytes(self) -> int:
+        return int(self.torch.cuda.mem_get_info(self.device_index)[0])
+
+    def ccsd(self, spatial, occupied, **kwargs):
+        """Spin-orbital CCSD on the device (``nbed_amd.ccsd_gpu.solve_spatial``): the capability the driver asks for."""
+        from . import ccsd_gpu
+
+        return ccsd_gpu.solve_spatial(spatial, occupied, backend=self, **kwargs)

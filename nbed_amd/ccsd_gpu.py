@@ -1,0 +1,371 @@
+"""Spin-orbital CCSD on the device: the equations of ``nbed_amd.ccsd`` with every contraction an ``nbx_gemm``.
+
+The reference runs PySCF's ``cc.CCSD`` on the embedded SCF object (nbed/driver.py:1105-1135).  ``nbed_amd.ccsd`` solves
+the same amplitude equations (Stanton, Gauss, Watts, Bartlett, J. Chem. Phys. 94, 4334 (1991), general Fock matrix) with
+dense numpy einsum on the host, for up to 40 spin orbitals.  This module is that solver on the MI355X:
+
+* the antisymmetrised blocks <pq||rs> are cut straight out of the three SPATIAL spin blocks of
+  ``HamiltonianBuilder.build_spatial()`` (``nbx_ccsd_gather``); the (2n)^4 tensor exists nowhere;
+* every term is a permute -> ``gemm`` -> permute (``Contractor``), the permutes one kernel (``nbx_permute4``) that also
+  does the P(ij), P(ab) antisymmetrisations of the doubles residual;
+* the particle-particle ladder 1/2 sum_ef tau_ijef <ab||ef> -- the only O(o^2 v^4) term -- runs over packed pairs
+  i < j, a < b, e < f, and W_abef is never formed: its t1 <ov||vv> pieces go through an o^3 v intermediate and its
+  1/4 tau <oo||vv> piece through W_mnij;
+* MP2 start, amplitude DIIS (space 6, from the second stored vector) and the convergence rule are those of
+  ``ccsd.solve``, so the iterates follow the host solver's and can be compared cycle by cycle.
+
+``torch`` only allocates and views; per cycle three groups of scalars reach the host (energy, max |err|, DIIS dots).
+"""
+
+from __future__ import annotations
+
+import itertools
+import time
+
+import numpy as np
+
+from .ccsd import CCSDResult
+from .exceptions import NbedDriverError
+
+# the nine blocks of <pq||rs> the equations read ('o' occupied, 'v' virtual) ...
+BLOCKS = ("oovv", "oooo", "ovvo", "ovov", "ooov", "ovvv", "vvvo", "ovoo")
+# ... and <vv||vv>, held over packed pairs (a < b, e < f) only
+
+
+def _npair(n: int) -> int:
+    return n * (n - 1) // 2
+
+
+def block_sizes(no: int, nv: int) -> dict:
+    """Doubles of every Hamiltonian block the solver keeps on the device for ``no`` occupied and ``nv`` virtual
+    spin orbitals (``vvvv`` over packed pairs)."""
+    ext = {"o": no, "v": nv}
+    sizes = {name: int(np.prod([ext[c] for c in name], dtype=object)) for name in BLOCKS}
+    sizes["vvvv"] = _npair(nv) ** 2
+    return sizes
+
+
+def memory_plan(no: int, nv: int, diis_space: int = 6) -> dict:
+    """Bytes the device solver needs, by group, computed before anything is allocated (host arithmetic):
+
+    blocks     the nine Hamiltonian blocks of ``block_sizes``
+    spatial    the (3, n, n, n, n) spatial spin blocks they are gathered from (2n = no + nv)
+    amplitudes [t1 | t2] and the residual of the same layout, the DIIS history (2 x space vectors), tau, tau~ and
+               the packed tau
+    work       the largest set of intermediates and permute buffers alive at once: W_mbej, the 1/2 t2 + t1 t1 of
+               its last term, three o^2 v^2 temporaries, two <ov||vv>-sized permute buffers, the packed ladder
+               result and its half-unpacked form
+    """
+    n = (no + nv + 1) // 2
+    nvec = no * nv + (no * nv) ** 2
+    o2v2 = (no * nv) ** 2
+    ovvv = no * nv**3
+    plan = {
+        "blocks": 8 * sum(block_sizes(no, nv).values()),
+        "spatial": 8 * 3 * n**4,
+        "amplitudes": 8 * (2 * nvec + 2 * diis_space * nvec + 2 * o2v2 + _npair(no) * _npair(nv)),
+        "work": 8 * (5 * o2v2 + 2 * ovvv + _npair(no) * _npair(nv) + _npair(no) * nv * nv + no**3 * nv + no**4),
+    }
+    plan["total"] = sum(plan.values())
+    return plan
+
+
+class Contractor:
+    """``out = alpha * einsum(spec, a, b) + beta * out`` for two operands of up to four axes as permute -> gemm -> permute.
+
+    Of the ways to lay the operands out as matrices -- free and contracted axes in the order of either operand or of the
+    result, either operand first -- the one that moves the fewest doubles through ``permute4`` is taken; an operand that
+    already is (free, contracted) or (contracted, free) is passed to the GEMM as it is, with 'N' or 'T'."""
+
+    def __init__(self, be):
+        self.be = be
+
+    @staticmethod
+    def _layout(letters, free, contr):
+        """('N' | 'T' | None) for an operand with axes ``letters`` used as a (free x contr) matrix."""
+        if list(letters) == free + contr:
+            return "N"
+        if list(letters) == contr + free:
+            return "T"
+        return None
+
+    def __call__(self, spec, a, b, alpha=1.0, out=None, beta=0.0):
+        be = self.be
+        ins, lo = spec.split("->")
+        la, lb = ins.split(",")
+        ext = {}
+        for letters, t in ((la, a), (lb, b)):
+            if len(letters) != t.dim():
+                raise ValueError(f"{spec}: operand of {t.dim()} axes")
+            for c, s in zip(letters, t.shape):
+                if ext.setdefault(c, int(s)) != int(s):
+                    raise ValueError(f"{spec}: extent of {c}")
+        contr_set = [c for c in la if c in lb and c not in lo]
+        if sorted(lo) != sorted(c for c in la + lb if c not in contr_set) or not contr_set:
+            raise ValueError(f"{spec}: not a two-operand contraction")
+        shape_out = tuple(ext[c] for c in lo)
+        if out is None:
+            if beta != 0.0:
+                raise ValueError("beta != 0 needs out")
+            out = be.empty(shape_out)
+        best = None
+        for swap in (False, True):
+            (l1, t1), (l2, t2) = ((lb, b), (la, a)) if swap else ((la, a), (lb, b))
+            f1_opts = {tuple(c for c in l1 if c in lo), tuple(c for c in lo if c in l1)}
+            f2_opts = {tuple(c for c in l2 if c in lo), tuple(c for c in lo if c in l2)}
+            k_opts = {tuple(c for c in l1 if c in contr_set), tuple(c for c in l2 if c in contr_set)}
+            for f1, f2, k in itertools.product(sorted(f1_opts), sorted(f2_opts), sorted(k_opts)):
+                f1, f2, k = list(f1), list(f2), list(k)
+                lay1, lay2 = self._layout(l1, f1, k), self._layout(l2, f2, k)
+                direct = f1 + f2 == list(lo)
+                cost = ((0 if lay1 else t1.numel()) + (0 if lay2 else t2.numel()) + (0 if direct else 2 * out.numel()))
+                if best is None or cost < best[0]:
+                    best = (cost, l1, t1, l2, t2, f1, f2, k, lay1, lay2, direct)
+        _, l1, t1, l2, t2, f1, f2, k, lay1, lay2, direct = best
+        m = int(np.prod([ext[c] for c in f1], dtype=np.int64))
+        n = int(np.prod([ext[c] for c in f2], dtype=np.int64))
+        kk = int(np.prod([ext[c] for c in k], dtype=np.int64))
+        if lay1 is None:
+            t1, lay1 = be.permute4(t1, [l1.index(c) for c in f1 + k]), "N"
+        if lay2 is None:
+            t2, lay2 = be.permute4(t2, [l2.index(c) for c in f2 + k]), "N"
+        ta = lay1  # (m x k) stored as is: 'N'; stored (k x m): 'T'
+        tb = "T" if lay2 == "N" else "N"  # the second operand enters the product as (k x n)
+        lda = kk if ta == "N" else m
+        ldb = kk if lay2 == "N" else n
+        if direct:
+            be.gemm_raw(ta, tb, m, n, kk, alpha, t1, lda, 0, t2, ldb, 0, beta, out, n, 0, 1)
+            return out
+        tmp = be.empty((m, n))
+        be.gemm_raw(ta, tb, m, n, kk, 1.0, t1, lda, 0, t2, ldb, 0, 0.0, tmp, n, 0, 1)
+        order = f1 + f2
+        be.permute4(tmp.view(tuple(ext[c] for c in order)), [order.index(c) for c in lo], alpha, beta, out)
+        return out
+
+
+def spatial_from_dense(h1: np.ndarray, h2: np.ndarray):
+    """(one_body (2,n,n), two_body (3,n,n,n,n)) of a dense spin-orbital Hamiltonian in the form ``build()`` returns
+    (alpha on the even indices; aaaa, bbbb, abba and baab the only non-zero spin blocks, baab the transpose of abba)."""
+    h1, h2 = np.asarray(h1, dtype=float), np.asarray(h2, dtype=float)
+    nso = h1.shape[0]
+    if nso % 2 or h1.shape != (nso, nso) or h2.shape != (nso,) * 4:
+        raise ValueError("solve() takes the (2n, 2n) / (2n)^4 spin-orbital tensors of HamiltonianBuilder.build()")
+    one = np.stack([h1[0::2, 0::2], h1[1::2, 1::2]])
+    two = np.stack([h2[0::2, 0::2, 0::2, 0::2], h2[1::2, 1::2, 1::2, 1::2], h2[0::2, 1::2, 1::2, 0::2]])
+    ok = not h1[0::2, 1::2].any() and not h1[1::2, 0::2].any()
+    ok = ok and np.array_equal(h2[1::2, 0::2, 0::2, 1::2], two[2].transpose(1, 0, 3, 2))
+    ok = ok and np.count_nonzero(h2) == sum(np.count_nonzero(x) for x in two) + np.count_nonzero(two[2])
+    if not ok:
+        raise ValueError("the dense Hamiltonian is not of the spin-block form HamiltonianBuilder.build() produces")
+    return np.ascontiguousarray(one), np.ascontiguousarray(two)
+
+
+def solve(constant, h1, h2, occupied, conv_tol: float = 1e-10, max_cycle: int = 200, diis_space: int = 6,
+          backend=None) -> CCSDResult:
+    """``ccsd.solve`` on the device, from the dense spin-orbital tensors of ``build()`` (direct use and tests; the driver
+    calls ``solve_spatial``, which never holds a (2n)^4 tensor)."""
+    one, two = spatial_from_dense(h1, h2)
+    return solve_spatial((constant, one, two), occupied, conv_tol=conv_tol, max_cycle=max_cycle, diis_space=diis_space,
+                         backend=backend)
+
+
+def _device_backend(backend):
+    if backend is None:
+        from .backend import get_backend
+
+        backend = get_backend()
+    if not hasattr(backend, "ccsd_gather"):
+        raise NbedDriverError(f"the device CCSD needs a HipBackend (got {type(backend).__name__})")
+    return backend
+
+
+def solve_spatial(spatial, occupied, conv_tol: float = 1e-10, max_cycle: int = 200, diis_space: int = 6, backend=None,
+                  stats: dict | None = None) -> CCSDResult:
+    """CCSD of the determinant that occupies the spin orbitals ``occupied`` (index 2p + s, alpha even).
+
+    ``spatial``: a ``SpatialHamiltonian``, or ``(constant, one_body (2,n,n), two_body (3,n,n,n,n))`` with the blocks of
+    ``build_spatial()`` (thresholded, the two-body ones halved) as host or device arrays.  ``stats``, if given, receives
+    the bytes planned and the seconds per cycle."""
+    be = _device_backend(backend)
+    if hasattr(spatial, "two_body"):
+        constant, one, two = spatial.constant, spatial.one_body, spatial.two_body
+    else:
+        constant, one, two = spatial
+    n = int(one.shape[-1])
+    nso = 2 * n
+    occ = sorted(int(i) for i in occupied)
+    if len(set(occ)) != len(occ) or (occ and (occ[0] < 0 or occ[-1] >= nso)):
+        raise ValueError("occupied: distinct spin-orbital indices in [0, 2n) expected")
+    vir = [p for p in range(nso) if p not in set(occ)]
+    no, nv = len(occ), len(vir)
+    if no == 0 or nv == 0:
+        raise ValueError("CCSD needs at least one occupied and one virtual spin orbital")
+    if not 1 <= diis_space <= 16:
+        raise ValueError("diis_space must be between 1 and 16")
+    plan = memory_plan(no, nv, diis_space)
+    held = 8 * 3 * n**4 if be.torch.is_tensor(two) and two.is_cuda else 0  # (device blocks are there already)
+    free = be.free_bytes()
+    if plan["total"] - held > free:
+        raise NbedDriverError(
+            f"device CCSD of {nso} spin orbitals ({no} occupied, {nv} virtual) needs {plan['total'] - held} bytes of "
+            f"device memory ({plan['blocks']} for the Hamiltonian blocks, {plan['amplitudes']} for amplitudes and DIIS "
+            f"history, {plan['work']} of work space); {free} are free")
+    if stats is not None:
+        stats.update(plan=plan, nso=nso, nocc=no, nvir=nv)
+
+    c = Contractor(be)
+    tb = be.asarray(two)
+    one_h = be.to_host(one)
+    h1 = np.zeros((nso, nso))
+    h1[0::2, 0::2], h1[1::2, 1::2] = one_h[0], one_h[1]
+    idx = {"o": be.index_array(occ, nso), "v": be.index_array(vir, nso)}
+    f = be.to_host(be.ccsd_fock(tb, be.asarray(h1), idx["o"]))
+    e_hf = float(constant) + 0.5 * float(np.sum(np.diag(h1)[occ]) + np.sum(np.diag(f)[occ]))
+    fov_h, foo_h, fvv_h = f[np.ix_(occ, vir)], f[np.ix_(occ, occ)], f[np.ix_(vir, vir)]
+    eo_h, ev_h = np.diag(foo_h).copy(), np.diag(fvv_h).copy()
+    fov, eo, ev = be.asarray(fov_h), be.asarray(eo_h), be.asarray(ev_h)
+    foo_od, fvv_od = be.asarray(foo_h - np.diag(eo_h)), be.asarray(fvv_h - np.diag(ev_h))
+
+    g = {name: be.ccsd_gather(tb, *(idx[ch] for ch in name)) for name in BLOCKS}
+    vvvv_p = be.ccsd_gather(tb, idx["v"], idx["v"], idx["v"], idx["v"], pack_first=True, pack_last=True)
+    del tb
+    oovv, oooo, ovvo, ovov, ooov, ovvv, vvvo, ovoo = (g[name] for name in BLOCKS)
+
+    n1, nvec = no * nv, no * nv + (no * nv) ** 2
+    hist_t, hist_e = be.empty((diis_space, nvec)), be.empty((diis_space, nvec))
+    amp, res = be.empty(nvec), be.empty(nvec)  # [t1 | t2] and the residual [r1 | r2]
+    t1, t2 = amp[:n1].view(no, nv), amp[n1:].view(no, no, nv, nv)
+    r1, r2 = res[:n1].view(no, nv), res[n1:].view(no, no, nv, nv)
+    maxerr = be.empty(1)
+    # MP2 start: t1 = 0, t2 = <ij||ab> / D  (the update kernel with r = [0 | oovv] and a scratch error vector)
+    res[:n1].zero_()
+    r2.copy_(oovv)
+    be.ccsd_update(no, nv, res, res, eo, ev, amp, hist_e[0], maxerr)
+
+    ident, swap_ab, swap_ij, swap_both = [0, 1, 2, 3], [0, 1, 3, 2], [1, 0, 2, 3], [1, 0, 3, 2]
+    oovv_flat, fov_flat = oovv.view(1, -1), fov.view(1, -1)
+
+    def energy(tau):
+        return float(be.dots(t1.reshape(-1), fov_flat)[0] + 0.25 * be.dots(tau.view(-1), oovv_flat)[0])
+
+    tau = be.ccsd_tau(t1, t2, 1.0, 1.0, 1.0)
+    e_old = energy(tau)
+    bmat = np.zeros((diis_space, diis_space))  # <err_s, err_t> by history slot
+    age = []  # history slots, oldest first
+    converged, it = False, 0
+    cycle_seconds = []
+    for it in range(1, max_cycle + 1):
+        t_start = time.perf_counter()
+        tau_t = be.ccsd_tau(t1, t2, 1.0, 0.5, 0.5)
+        # intermediates (eqs. 3-8 of Stanton et al.), off-diagonal Fock terms kept
+        fae = be.copy(fvv_od)
+        c("me,ma->ae", fov, t1, -0.5, fae, 1.0)
+        c("mf,mafe->ae", t1, ovvv, 1.0, fae, 1.0)
+        c("mnaf,mnef->ae", tau_t, oovv, -0.5, fae, 1.0)
+        fmi = be.copy(foo_od)
+        c("ie,me->mi", t1, fov, 0.5, fmi, 1.0)
+        c("ne,mnie->mi", t1, ooov, 1.0, fmi, 1.0)
+        c("inef,mnef->mi", tau_t, oovv, 0.5, fmi, 1.0)
+        del tau_t
+        fme = be.copy(fov)
+        c("nf,mnef->me", t1, oovv, 1.0, fme, 1.0)
+        # W_mnij plus the 1/4 tau <oo||vv> piece of W_abef: 1/2 tau_ijef W_abef contains 1/2 tau_mnab (1/4 tau_ijef <mn||ef>)
+        wmnij = be.copy(oooo)
+        c("je,mnie->mnij", t1, ooov, 1.0, wmnij, 1.0)
+        c("ie,mnje->mnij", t1, ooov, -1.0, wmnij, 1.0)
+        c("ijef,mnef->mnij", tau, oovv, 0.5, wmnij, 1.0)
+        wmbej = be.copy(ovvo)
+        c("jf,mbef->mbej", t1, ovvv, 1.0, wmbej, 1.0)
+        c("nb,mnje->mbej", t1, ooov, 1.0, wmbej, 1.0)
+        half = be.ccsd_tau(t1, t2, 0.5, 1.0, 0.0)  # 1/2 t2_jnfb + t1_jf t1_nb
+        c("jnfb,mnef->mbej", half, oovv, -1.0, wmbej, 1.0)
+        del half
+        # T1 (eq. 1)
+        r1.copy_(fov)
+        c("ie,ae->ia", t1, fae, 1.0, r1, 1.0)
+        c("ma,mi->ia", t1, fmi, -1.0, r1, 1.0)
+        c("imae,me->ia", t2, fme, 1.0, r1, 1.0)
+        c("nf,naif->ia", t1, ovov, -1.0, r1, 1.0)
+        c("imef,maef->ia", t2, ovvv, -0.5, r1, 1.0)
+        c("mnae,nmie->ia", t2, ooov, 0.5, r1, 1.0)
+        # T2 (eq. 2)
+        r2.copy_(oovv)
+        c("mb,me->be", t1, fme, -0.5, fae, 1.0)
+        tmp = c("ijae,be->ijab", t2, fae)
+        be.permute4(tmp, ident, 1.0, 1.0, r2)
+        be.permute4(tmp, swap_ab, -1.0, 1.0, r2)
+        c("je,me->mj", t1, fme, 0.5, fmi, 1.0)
+        c("imab,mj->ijab", t2, fmi, 1.0, tmp, 0.0)
+        be.permute4(tmp, ident, -1.0, 1.0, r2)
+        be.permute4(tmp, swap_ij, 1.0, 1.0, r2)
+        c("mnab,mnij->ijab", tau, wmnij, 0.5, r2, 1.0)
+        # the ladder over packed pairs: sum_{e<f} tau_(ij)(ef) <ab||ef>_(ab)(ef)
+        tau_p = be.ccsd_tau(t1, t2, 1.0, 1.0, 1.0, packed=True)
+        npo, npv = _npair(no), _npair(nv)
+        if npo and npv:
+            lad = be.empty((npo, npv))
+            be.gemm_raw("N", "T", npo, npv, npv, 1.0, tau_p, npv, 0, vvvv_p, npv, 0, 0.0, lad, npv, 0, 1)
+            lad_ab = be.pair_unpack(lad, npo, nv, 1)               # (i<j, a, b)
+            be.pair_unpack(lad_ab, 1, no, nv * nv, 1.0, 1.0, r2)   # r2 += (i, j, a, b)
+            del lad, lad_ab
+        del tau_p
+        # the t1 <ov||vv> pieces of W_abef through Z_ijma = 1/2 sum_ef tau_ijef <ma||ef>
+        z = c("ijef,maef->ijma", tau, ovvv, 0.5)
+        c("ijma,mb->ijab", z, t1, 1.0, tmp, 0.0)
+        del z
+        be.permute4(tmp, ident, 1.0, 1.0, r2)
+        be.permute4(tmp, swap_ab, -1.0, 1.0, r2)
+        c("imae,mbej->ijab", t2, wmbej, 1.0, tmp, 0.0)
+        y = c("ie,mbej->imbj", t1, ovvo)
+        c("ma,imbj->ijab", t1, y, -1.0, tmp, 1.0)
+        del y
+        be.permute4(tmp, ident, 1.0, 1.0, r2)
+        be.permute4(tmp, swap_ij, -1.0, 1.0, r2)
+        be.permute4(tmp, swap_ab, -1.0, 1.0, r2)
+        be.permute4(tmp, swap_both, 1.0, 1.0, r2)
+        c("ie,abej->ijab", t1, vvvo, 1.0, tmp, 0.0)
+        be.permute4(tmp, ident, 1.0, 1.0, r2)
+        be.permute4(tmp, swap_ij, -1.0, 1.0, r2)
+        c("ma,mbij->ijab", t1, ovoo, 1.0, tmp, 0.0)
+        be.permute4(tmp, ident, -1.0, 1.0, r2)
+        be.permute4(tmp, swap_ab, 1.0, 1.0, r2)
+        del tmp, wmbej, wmnij, fae, fmi, fme
+        # t_new = r / D and err = t_new - t into the next history slot; DIIS on the amplitudes
+        slot = (it - 1) % diis_space
+        be.ccsd_update(no, nv, res, amp, eo, ev, hist_t[slot], hist_e[slot], maxerr)
+        if slot in age:
+            age.remove(slot)
+        age.append(slot)
+        m = len(age)
+        row = be.dots(hist_e[slot], hist_e[:m] if m < diis_space else hist_e)
+        bmat[slot, : len(row)] = row
+        bmat[: len(row), slot] = row
+        err_max = float(be.read_scalars(maxerr)[0])
+        coef = None
+        if m > 1:
+            b = -np.ones((m + 1, m + 1))
+            b[m, m] = 0.0
+            b[:m, :m] = bmat[np.ix_(age, age)]
+            rhs = np.zeros(m + 1)
+            rhs[m] = -1.0
+            try:
+                sol = np.linalg.solve(b, rhs)[:m]
+                coef = np.zeros(m)
+                coef[age] = sol
+            except np.linalg.LinAlgError:
+                pass
+        if coef is None:
+            amp.copy_(hist_t[slot])
+        else:
+            be.lincomb(coef, hist_t[:m], out=amp)
+        tau = be.ccsd_tau(t1, t2, 1.0, 1.0, 1.0)
+        e_new = energy(tau)
+        cycle_seconds.append(time.perf_counter() - t_start)
+        done = abs(e_new - e_old) < conv_tol and err_max < max(conv_tol, 1e-9) * 10
+        e_old = e_new
+        if done:
+            converged = True
+            break
+    if stats is not None:
+        stats.update(cycle_seconds=cycle_seconds, iterations=it)
+    return CCSDResult(e_hf, e_old, be.to_host(t1).copy(), be.to_host(t2).copy(), converged, it)

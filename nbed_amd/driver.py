@@ -28,6 +28,7 @@ branch binds a boolean (:918) and is not reproduced.
 from __future__ import annotations
 
 import logging
+import os
 from functools import cached_property
 from typing import Optional
 
@@ -365,17 +366,24 @@ class NbedDriver:
         self._unsupported("The global Hartree-Fock reference calculation")
 
     def _ccsd_of(self, scf_obj, frozen=None):
-        """CCSD of an SCF object: PySCF's solver where there is one, else -- for small orbital spaces -- the
-        spin-orbital equations over the Hamiltonian ``HamiltonianBuilder`` makes of it (``nbed_amd.ccsd``)."""
+        """CCSD of an SCF object: PySCF's solver where there is one, else the spin-orbital equations over the
+        Hamiltonian ``HamiltonianBuilder`` makes of it -- on the host for small orbital spaces (``nbed_amd.ccsd``), on
+        the device above its cap when the backend offers ``ccsd`` (``nbed_amd.ccsd_gpu``).  ``NBED_CCSD_SOLVER`` =
+        ``auto`` (default) | ``host`` | ``device`` forces either of the two at any size it accepts."""
+        mode = os.environ.get("NBED_CCSD_SOLVER", "auto")
+        if mode not in ("auto", "host", "device"):
+            raise NbedDriverError(f"NBED_CCSD_SOLVER={mode!r}: expected 'auto', 'host' or 'device'")
         try:
             return run_emb_ccsd(scf_obj, frozen, self.config.convergence, self.config.max_ram_memory)[0]
         except NbedDriverError:
             from . import ccsd
 
             n = np.asarray(scf_obj.mo_coeff).shape[-1]
-            if frozen is not None or 2 * n > ccsd.MAX_SPIN_ORBITALS:
+            on_device = mode == "device" or (mode == "auto" and 2 * n > ccsd.MAX_SPIN_ORBITALS)
+            if frozen is not None or (on_device and not hasattr(self.be, "ccsd")) or (
+                    not on_device and 2 * n > ccsd.MAX_SPIN_ORBITALS):
                 raise
-            const, h1, h2 = HamiltonianBuilder(scf_obj, scf_obj.energy_nuc(), backend=self.be).build()
+            builder = HamiltonianBuilder(scf_obj, scf_obj.energy_nuc(), backend=self.be)
             # the reference determinant from the object's own occupations (alpha on the even spin-orbital indices):
             # after the environment is deleted / the virtuals are re-ordered the occupied MOs need not lead
             mo_occ = np.asarray(scf_obj.mo_occ)
@@ -387,7 +395,11 @@ class NbedDriver:
             if (int(np.sum(mo_occ[0] > 0)), int(np.sum(mo_occ[1] > 0))) != (int(na), int(nb)):
                 raise NbedDriverError(f"mo_occ holds {int(np.sum(mo_occ[0] > 0))} + {int(np.sum(mo_occ[1] > 0))} occupied "
                                       f"orbitals, the molecule {na} + {nb} electrons")
-            return ccsd.solve(const, h1, h2, occupied, conv_tol=min(self.config.convergence, 1e-8))
+            conv_tol = min(self.config.convergence, 1e-8)
+            if on_device:  # the three spatial spin blocks stay on the device; no (2n)^4 tensor anywhere
+                return self.be.ccsd(builder.build_spatial_device(), occupied, conv_tol=conv_tol)
+            const, h1, h2 = builder.build()
+            return ccsd.solve(const, h1, h2, occupied, conv_tol=conv_tol)
 
     @cached_property
     def _global_ccsd(self):

@@ -178,6 +178,13 @@ class HamiltonianBuilder:
         """The same Hamiltonian as ``build()`` kept in its three unique spatial spin blocks (not in the
         reference: its (2n)^4 output is 60 GB per projector at n = 147, almost all of it zeros and
         copies; this form is 6.4 GB and reaches the host 16/3 times sooner)."""
+        be = self.be
+        constant, one, two = self.build_spatial_device()
+        return SpatialHamiltonian(constant, be.to_host(one), be.to_host(two))
+
+    def build_spatial_device(self):
+        """``(constant, one_body, two_body)`` of ``build_spatial()`` left on the device: what a consumer that
+        runs there (``nbed_amd.ccsd_gpu.solve_spatial``) reads without a round trip through the host."""
         if self.n_frozen_virt != 0:
             self.scf_method = reduce_virtuals(self.scf_method, self.n_frozen_virt)
         be = self.be
@@ -185,7 +192,7 @@ class HamiltonianBuilder:
         be.threshold_scale(one, EQ_TOLERANCE, 1.0)
         two = self._two_body_device(blocks=3)  # aaaa, bbbb, aabb (physicist order); bbaa is never formed
         be.threshold_scale(two, EQ_TOLERANCE, 0.5)
-        return SpatialHamiltonian(self.constant_e_shift, be.to_host(one), be.to_host(two))
+        return self.constant_e_shift, one, two
 
     def build(self) -> tuple[float, np.ndarray, np.ndarray]:
         """Second-quantised fermionic Hamiltonian: (constant, h1, 0.5 * h2)."""
