@@ -791,6 +791,42 @@ int nbx_ccsd_tau(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_t1, c
 int nbx_ccsd_update(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_r, const double* d_t_old,
                     const double* d_eo, const double* d_ev, double* d_t_new, double* d_err, double* d_maxerr);
 
+/* ------------------------------------------------------------------ full CI (csrc/fci.hip)
+ * What surrounds the GEMM of a determinant FCI sigma build (nbed_amd/fci_gpu.py): the reference runs PySCF's
+ * fci.FCI on the embedded object (nbed/driver.py:1044-1102); here H c is formed on the device from the three
+ * spatial spin blocks d_two_body (3, n, n, n, n) and d_one_body (2, n, n) of build_spatial().  A determinant is
+ * (alpha string, beta string); strings are ranked lexicographically by their ascending lists of occupied
+ * orbitals, the CI vector is row-major (n_alpha_str, n_beta_str), determinant indices are 64-bit.  With
+ * E_ps = a+_p a_s,  a+_p a+_q a_r a_s = E_ps E_qr - delta_qs E_pr, so
+ *      H = const + sum_g k_g E_g + sum_{g g'} G[g, g'] E_g E_g',     g = (spin, p, s) = spin n^2 + p n + s,
+ *      G[(a,ps),(a,qr)] = aaaa[p,q,r,s], G[(b,ps),(b,qr)] = bbbb[p,q,r,s], G[(a,ps),(b,qr)] = aabb[p,q,r,s],
+ *      G[(b,ps),(a,qr)] = aabb[q,p,s,r],  k_(s,pr) = one_body[s][p,r] - sum_q two_body[ss][p,q,r,q].
+ * Link tables (int, built by the caller): link[S, k n + l] = sign (rank + 1) of E_kl |S>, 0 where it
+ * vanishes; d_link_a is (n_alpha_str, n^2), d_link_bt the TRANSPOSED beta table (n^2, n_beta_str).  The kernels
+ * trust them.  n <= 31, n_beta_str <= 13312 (a row is staged in LDS).  None of these synchronises.
+ *
+ * d_g (2 n^2, 2 n^2 + 1) = [G | k].                                                                     */
+int nbx_fci_gmat(nbx_ctx* ctx, int64_t n, const double* d_one_body, const double* d_two_body, double* d_g);
+/* d_d (2 n^2 + 1, rows n_beta_str): D[g, K] = <K| E_g |c> for the determinants K of alpha rows
+ * [row0, row0 + rows), and c itself in the last row, so that E = d_g . d_d carries the k term.      */
+int nbx_fci_gather(nbx_ctx* ctx, int64_t n, int64_t n_alpha_str, int64_t n_beta_str, int64_t row0, int64_t rows,
+                   const int* d_link_a, const int* d_link_bt, const double* d_c, double* d_d);
+/* sigma_I = (accumulate ? sigma_I : shift c_I) + sum_{g, K in the chunk} <I| E_g |K> E[g, K] over ALL I, d_e
+ * (2 n^2, rows n_beta_str).  One gather per output element, summed in a fixed order, no atomics: the same
+ * chunks in the same order give the same bits.                                                        */
+int nbx_fci_scatter(nbx_ctx* ctx, int64_t n, int64_t n_alpha_str, int64_t n_beta_str, int64_t row0, int64_t rows,
+                    const int* d_link_a, const int* d_link_bt, const double* d_e, double shift, const double* d_c,
+                    int accumulate, double* d_sigma);
+/* d_diag[I] = H_II = constant + sum_{P in I} h1[P,P] + sum_{P != Q in I} (h2[P,Q,Q,P] - h2[P,Q,P,Q]); d_str_a /
+ * d_str_b: the bit masks of the ranked strings (the Davidson preconditioner of the solver that stands in for
+ * fci.FCI.kernel, nbed/driver.py:1044-1102).                                                         */
+int nbx_fci_diag(nbx_ctx* ctx, int64_t n, int64_t n_alpha_str, int64_t n_beta_str, const int* d_str_a,
+                 const int* d_str_b, const double* d_one_body, const double* d_two_body, double constant,
+                 double* d_diag);
+/* Davidson correction out = r / (diag - theta), |diag - theta| < guard replaced by +-guard.         */
+int nbx_fci_precond(nbx_ctx* ctx, int64_t ndet, double theta, double guard, const double* d_r, const double* d_diag,
+                    double* d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -931,6 +931,8 @@ class HipBackend:
 
     def lincomb(self, coef, vecs, out=None):
         nvec, n = vecs.shape[0], vecs[0].numel()
+        if len(coef) != nvec:
+            raise ValueError(f"lincomb: {len(coef)} coefficients for {nvec} vectors")
         if out is None:
             out = self.empty(vecs.shape[1:])
         c = (c_double * nvec)(*[float(x) for x in coef])
@@ -1502,3 +1504,51 @@ class HipBackend:
         from . import ccsd_gpu
 
         return ccsd_gpu.solve_spatial(spatial, occupied, backend=self, **kwargs)
+
+    # ------------------------------------------------------------------ full CI (csrc/fci.hip)
+    def int_array(self, a):
+        """Host integers -> contiguous device int32 array (string masks and link tables of ``fci_gpu``)."""
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    def fci_gmat(self, one_body, two_body):
+        """[G | k] (2n^2, 2n^2 + 1) of the generator form of the Hamiltonian (include/nbx.h, "full CI")."""
+        n = int(two_body.shape[-1])
+        out = self.empty((2 * n * n, 2 * n * n + 1))
+        self._call("nbx_fci_gmat", n, self._p(one_body), self._p(two_body), self._p(out))
+        return out
+
+    def fci_gather(self, n: int, na_str: int, nb_str: int, row0: int, rows: int, link_a, link_bt, c, d):
+        """d (2n^2 + 1, rows * nb_str) = <K|E_g|c> over the alpha rows [row0, row0 + rows), c in the last row."""
+        if c.numel() != na_str * nb_str or d.numel() != (2 * n * n + 1) * rows * nb_str:
+            raise ValueError("fci_gather: shape")
+        self._call("nbx_fci_gather", n, na_str, nb_str, row0, rows, self._p(link_a), self._p(link_bt), self._p(c),
+                   self._p(d))
+
+    def fci_scatter(self, n: int, na_str: int, nb_str: int, row0: int, rows: int, link_a, link_bt, e, shift: float, c,
+                    accumulate: bool, sigma):
+        """sigma = (accumulate ? sigma : shift * c) + sum_g E_g e[g] over the chunk's determinants."""
+        if (c.numel() != na_str * nb_str or sigma.numel() != na_str * nb_str
+                or e.numel() != 2 * n * n * rows * nb_str):
+            raise ValueError("fci_scatter: shape")
+        self._call("nbx_fci_scatter", n, na_str, nb_str, row0, rows, self._p(link_a), self._p(link_bt), self._p(e),
+                   float(shift), self._p(c), int(accumulate), self._p(sigma))
+
+    def fci_diag(self, n: int, str_a, str_b, one_body, two_body, constant: float):
+        """H_II over the (alpha string, beta string) determinants, (Na, Nb)."""
+        out = self.empty((int(str_a.numel()), int(str_b.numel())))
+        self._call("nbx_fci_diag", n, int(str_a.numel()), int(str_b.numel()), self._p(str_a), self._p(str_b),
+                   self._p(one_body), self._p(two_body), float(constant), self._p(out))
+        return out
+
+    def fci_precond(self, r, diag, theta: float, guard: float, out):
+        """out = r / (diag - theta), small denominators held at +-guard (the Davidson correction)."""
+        if diag.numel() != r.numel() or out.numel() != r.numel():
+            raise ValueError("fci_precond: shape")
+        self._call("nbx_fci_precond", int(r.numel()), float(theta), float(guard), self._p(r), self._p(diag), self._p(out))
+        return out
+
+    def fci(self, spatial, nelec, occupied=None, **kwargs):
+        """Determinant FCI on the device (``nbed_amd.fci_gpu.solve_spatial``): the capability the driver asks for."""
+        from . import fci_gpu
+
+        return fci_gpu.solve_spatial(spatial, nelec, occupied, backend=self, **kwargs)

@@ -406,20 +406,48 @@ class NbedDriver:
         """Global CCSD reference (nbed/driver.py:122-136)."""
         return self._ccsd_of(self._global_hf)
 
-    @cached_property
-    def _global_fci(self):
-        """Global FCI reference (nbed/driver.py:139-153): PySCF's solver on the global HF object, or for
-        small molecules the exact diagonalisation of its full-space Hamiltonian (``nbed_amd.fci``)."""
-        hf = self._global_hf
+    def _fci_of(self, scf_obj, frozen=None):
+        """FCI of an SCF object: PySCF's solver where there is one, else the ground state of the Hamiltonian
+        ``HamiltonianBuilder`` makes of it (nuclear repulsion as its constant: what PySCF's FCI object reports as e_tot,
+        tests/test_builder.py:55-120) -- diagonalised on the host for small orbital spaces (``nbed_amd.fci``), by the
+        device solver above its cap when the backend offers ``fci`` (``nbed_amd.fci_gpu``).  ``NBED_FCI_SOLVER`` =
+        ``auto`` (default) | ``host`` | ``device`` forces either of the two at any size it accepts."""
+        mode = os.environ.get("NBED_FCI_SOLVER", "auto")
+        if mode not in ("auto", "host", "device"):
+            raise NbedDriverError(f"NBED_FCI_SOLVER={mode!r}: expected 'auto', 'host' or 'device'")
         try:
-            return run_emb_fci(hf, None, self.config.convergence, self.config.max_ram_memory)
+            return run_emb_fci(scf_obj, frozen, self.config.convergence, self.config.max_ram_memory)
         except NbedDriverError:
             from . import fci
 
-            if 2 * np.asarray(hf.mo_coeff).shape[-1] > fci.MAX_SPIN_ORBITALS:
+            n = np.asarray(scf_obj.mo_coeff).shape[-1]
+            on_device = mode == "device" or (mode == "auto" and 2 * n > fci.MAX_SPIN_ORBITALS)
+            if frozen is not None or (on_device and not hasattr(self.be, "fci")) or (
+                    not on_device and 2 * n > fci.MAX_SPIN_ORBITALS):
                 raise
-            const, h1, h2 = HamiltonianBuilder(hf, hf.energy_nuc(), backend=self.be).build()
-            return fci.ground_state(const, h1, h2, hf.mol.nelec)
+            builder = HamiltonianBuilder(scf_obj, scf_obj.energy_nuc(), backend=self.be)
+            if not on_device:
+                const, h1, h2 = builder.build()
+                return fci.ground_state(const, h1, h2, scf_obj.mol.nelec)
+            # the start determinant from the object's own occupations, read as _ccsd_of reads them
+            mo_occ = np.asarray(scf_obj.mo_occ)
+            if mo_occ.ndim == 1:
+                mo_occ = np.array((mo_occ > 0, mo_occ > 1), dtype=float)  # (alpha holds the singly occupied orbitals)
+            occupied = ([2 * int(i) for i in np.flatnonzero(mo_occ[0] > 0)]
+                        + [2 * int(i) + 1 for i in np.flatnonzero(mo_occ[1] > 0)])
+            na, nb = scf_obj.mol.nelec
+            if (int(np.sum(mo_occ[0] > 0)), int(np.sum(mo_occ[1] > 0))) != (int(na), int(nb)):
+                raise NbedDriverError(f"mo_occ holds {int(np.sum(mo_occ[0] > 0))} + {int(np.sum(mo_occ[1] > 0))} occupied "
+                                      f"orbitals, the molecule {na} + {nb} electrons")
+            # the three spatial spin blocks stay on the device; no (2n)^4 tensor anywhere
+            return self.be.fci(builder.build_spatial_device(), (int(na), int(nb)), occupied,
+                               conv_tol=min(self.config.convergence, 1e-8))
+
+    @cached_property
+    def _global_fci(self):
+        """Global FCI reference (nbed/driver.py:139-153): PySCF's solver on the global HF object, or the ground state of
+        its full-space Hamiltonian (``_fci_of``)."""
+        return self._fci_of(self._global_hf)
 
     # ------------------------------------------------------------------ localisation
     def _localize(self) -> LocalizedSystem:
@@ -634,20 +662,9 @@ class NbedDriver:
         return cc, cc.e_corr
 
     def _run_emb_fci(self, emb_scf, frozen=None):
-        """driver.py:476-498.  Without PySCF, small active spaces are diagonalised exactly from the
-        active-space Hamiltonian of this same embedded object (``nbed_amd.fci``)."""
-        try:
-            return run_emb_fci(emb_scf, frozen, self.config.convergence, self.config.max_ram_memory)
-        except NbedDriverError:
-            from . import fci
-
-            n = np.asarray(emb_scf.mo_coeff).shape[-1]
-            if frozen is not None or 2 * n > fci.MAX_SPIN_ORBITALS:
-                raise
-            # Hamiltonian with the nuclear repulsion as its constant: its ground state is what PySCF's
-            # FCI object reports as e_tot (tests/test_builder.py:55-120)
-            const, h1, h2 = HamiltonianBuilder(emb_scf, emb_scf.energy_nuc(), backend=self.be).build()
-            return fci.ground_state(const, h1, h2, emb_scf.mol.nelec)
+        """driver.py:476-498.  Without PySCF the ground state of the active-space Hamiltonian of this same embedded
+        object: ``nbed_amd.fci`` on the host for small active spaces, ``nbed_amd.fci_gpu`` on the device above."""
+        return self._fci_of(emb_scf, frozen)
 
     # ------------------------------------------------------------------ the embedding
     def embed(self, init_huzinaga_rhf_with_mu: bool = False,
