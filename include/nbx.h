@@ -242,6 +242,20 @@ int nbx_gemm(nbx_ctx* ctx, char trans_a, char trans_b, int64_t m, int64_t n, int
              double alpha, const double* d_a, int64_t lda, int64_t stride_a,
              const double* d_b, int64_t ldb, int64_t stride_b, double beta,
              double* d_c, int64_t ldc, int64_t stride_c, int64_t batch);
+/* Test support: which kernel nbx_gemm runs a product on -- the function its launcher calls, host arithmetic only
+ * (no context, no GPU; NBX_GEMM_DMA in the environment is honoured as the launcher honours it).  vec_a / vec_b:
+ * 1 = the operand has a 16-byte aligned base and even ld and batch stride (what nbx_gemm derives from its
+ * arguments), 0 = it is staged element by element.  A batch past 65535 runs in chunks: the answer is for the first.
+ * tests/gemm_cases.py keeps a shape per kernel and layout and tests/test_host_gemm_cases.py fails when a retuned
+ * threshold moves one of them to another kernel.                                                              */
+#define NBX_GEMM_KERNEL_NONE 0   /* nothing launched (m, n or batch == 0) */
+#define NBX_GEMM_KERNEL_SMALL 1  /* gemm_small_kernel: one wave per 16 x 16 tile, operands straight from memory */
+#define NBX_GEMM_KERNEL_T32 2    /* gemm_f64_kernel, 32 x 32 tiles */
+#define NBX_GEMM_KERNEL_T64 3    /* gemm_f64_kernel, 64 x 64 tiles */
+#define NBX_GEMM_KERNEL_T128 4   /* gemm_f64_kernel, 128 x 128 tiles */
+#define NBX_GEMM_KERNEL_TN_DMA 5 /* gemm_m4_tn_kernel: 'T','N' only, k-tiles brought into LDS by the load unit */
+int nbx_gemm_route(char trans_a, char trans_b, int64_t m, int64_t n, int64_t k, int64_t batch, int vec_a,
+                   int vec_b);
 
 /* ------------------------------------------------------------------ Fock assembly & reductions */
 /* F[x] = hcore[x or 0] + vemb[x] + J - K[x]  (x < 2); d_jk as written by nbx_jk_dense with

@@ -28,6 +28,8 @@ HUZ_JK_PACKED, HUZ_JK_SYM = 0, 1
 XC_CODES = {"slater": 0, "lda": 1, "lda,vwn_rpa": 1, "lda,vwn": 2, "lda,vwn5": 2, "svwn": 2, "b3lyp": 3}
 
 PROF_JK_DENSE, PROF_AO2MO_Q1, PROF_AO2MO, PROF_EIGH, PROF_SVD, PROF_GEMM = range(6)
+# nbx_gemm_route answers (NBX_GEMM_KERNEL_*)
+GEMM_KERNEL_NONE, GEMM_KERNEL_SMALL, GEMM_KERNEL_T32, GEMM_KERNEL_T64, GEMM_KERNEL_T128, GEMM_KERNEL_TN_DMA = range(6)
 
 
 class NbxError(RuntimeError):
@@ -105,6 +107,7 @@ SIGNATURES = {
     "nbx_jk_synth": (c_int, [_P, c_int64, c_int64, c_int64, c_uint64, _P, c_int64, _P, _P, c_size_t]),
     "nbx_gemm": (c_int, [_P, c_char, c_char, c_int64, c_int64, c_int64, c_double, _P, c_int64, c_int64,
                          _P, c_int64, c_int64, c_double, _P, c_int64, c_int64, c_int64]),
+    "nbx_gemm_route": (c_int, [c_char, c_char, c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
     "nbx_fock_uhf": (c_int, [_P, c_int64, _P, c_int, _P, _P, _P, _P]),
     "nbx_huzinaga_sym": (c_int, [_P, c_int64, c_int64, _P, c_double, _P, _P]),
     "nbx_trace_prod": (c_int, [_P, c_int64, c_int64, _P, _P, POINTER(c_double)]),

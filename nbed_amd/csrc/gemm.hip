@@ -638,6 +638,21 @@ void launch_tn_dma(nbx_ctx* ctx, int M, int N, int K, double alpha, const double
                        C, ldc, sc, pair_n, gate, gate_a, gate_b, GemmGen{});
 }
 
+// Which kernel one batch chunk (nb <= 65535 entries) of nbx_gemm runs on: the only place that decides it
+// (nbx_gemm_gated launches what this returns, nbx_gemm_route reports it).
+int gemm_route(bool a_kc, bool b_kc, int64_t m, int64_t n, int64_t k, int64_t nb, int vec_a, int vec_b) {
+    const int64_t tiles128 = nbx_cdiv(m, 128) * nbx_cdiv(n, 128) * nb;
+    const int64_t tiles16 = nbx_cdiv(m, 16) * nbx_cdiv(n, 16) * nb;
+    if (tiles16 <= 512 && k <= 4096) return NBX_GEMM_KERNEL_SMALL;
+    if ((tiles128 >= 512 || (tiles128 >= 128 && k >= 2048)) && !a_kc && !b_kc && tn_dma_ok(m, n, k, vec_a, vec_b))
+        return NBX_GEMM_KERNEL_TN_DMA;
+    if (tiles128 >= 512 && m > 64 && n > 64) return NBX_GEMM_KERNEL_T128;
+    // (also where 64 x 64 tiles would leave half the chip idle -- the 64-row panels of the blocked
+    //  back-transformation, csrc/eigh_grid.hip, batched matrices of a few hundred rows: four times the workgroups)
+    if (m <= 32 || n <= 32 || nbx_cdiv(m, 64) * nbx_cdiv(n, 64) * nb < 128) return NBX_GEMM_KERNEL_T32;
+    return NBX_GEMM_KERNEL_T64;
+}
+
 }  // namespace
 
 // Y[z] (m x n) = op(A) (m x k) . G_z (k x n),  G_z[p][q] = val(canon(p, q, r, s0 + z)) * scale,
@@ -753,6 +768,17 @@ int nbx_gemm_pair_scatter(nbx_ctx* ctx, int64_t pair_n, int64_t m, int64_t n, in
     return NBX_OK;
 }
 
+// Test support: the kernel nbx_gemm runs a product on (the first chunk of a batch past 65535), host arithmetic only.
+// vec_a / vec_b: what nbx_gemm derives from the operands' addresses (16-byte aligned base, even ld and batch stride).
+extern "C" int nbx_gemm_route(char trans_a, char trans_b, int64_t m, int64_t n, int64_t k, int64_t batch, int vec_a,
+                              int vec_b) {
+    if (m <= 0 || n <= 0 || batch <= 0) return NBX_GEMM_KERNEL_NONE;
+    const bool ta = (trans_a == 'T' || trans_a == 't');
+    const bool tb = (trans_b == 'T' || trans_b == 't');
+    const int64_t nb = batch < 65535 ? batch : 65535;
+    return gemm_route(!ta, tb, m, n, k, nb, (k > 0 && vec_a) ? 1 : 0, (k > 0 && vec_b) ? 1 : 0);
+}
+
 extern "C" int nbx_gemm(nbx_ctx* ctx, char trans_a, char trans_b, int64_t m, int64_t n, int64_t k,
                         double alpha, const double* d_a, int64_t lda, int64_t stride_a, const double* d_b,
                         int64_t ldb, int64_t stride_b, double beta, double* d_c, int64_t ldc,
@@ -794,9 +820,8 @@ int nbx_gemm_gated(nbx_ctx* ctx, char trans_a, char trans_b, int64_t m, int64_t 
         const double* A = d_a ? d_a + b0 * stride_a : nullptr;
         const double* B = d_b ? d_b + b0 * stride_b : nullptr;
         double* C = d_c + b0 * stride_c;
-        const int64_t tiles128 = nbx_cdiv(m, 128) * nbx_cdiv(n, 128) * nb;
-        const int64_t tiles16 = nbx_cdiv(m, 16) * nbx_cdiv(n, 16) * nb;
-        if (tiles16 <= 512 && k <= 4096) {
+        switch (gemm_route(a_kc, b_kc, m, n, k, nb, vec_a, vec_b)) {
+        case NBX_GEMM_KERNEL_SMALL: {
             dim3 grid((unsigned)nbx_cdiv(n, 16), (unsigned)nbx_cdiv(m, 16), (unsigned)nb);
 #define NBX_GEMM_SMALL(AK, BKC)                                                                               \
     hipLaunchKernelGGL((gemm_small_kernel<AK, BKC>), grid, dim3(64), 0, ctx->stream, (int)m, (int)n, (int)k, \
@@ -810,20 +835,24 @@ int nbx_gemm_gated(nbx_ctx* ctx, char trans_a, char trans_b, int64_t m, int64_t 
                 else NBX_GEMM_SMALL(false, false);
             }
 #undef NBX_GEMM_SMALL
-        } else if ((tiles128 >= 512 || (tiles128 >= 128 && k >= 2048)) && !a_kc && !b_kc && tn_dma_ok(m, n, k, vec_a, vec_b)) {
+            break;
+        }
+        case NBX_GEMM_KERNEL_TN_DMA:
             launch_tn_dma(ctx, (int)m, (int)n, (int)k, alpha, A, lda, stride_a, B, ldb, stride_b, beta, C, ldc, stride_c, nb,
                           0, d_gate, gate_a, gate_b);
-        } else if (tiles128 >= 512 && m > 64 && n > 64) {
+            break;
+        case NBX_GEMM_KERNEL_T128:
             launch<128, 128, 2, 4>(ctx, a_kc, b_kc, (int)m, (int)n, (int)k, alpha, A, lda, stride_a, B, ldb, stride_b,
                              beta, C, ldc, stride_c, nb, vec_a, vec_b, d_gate, gate_a, gate_b);
-        } else if (m <= 32 || n <= 32 || nbx_cdiv(m, 64) * nbx_cdiv(n, 64) * nb < 128) {
-            // (also where 64 x 64 tiles would leave half the chip idle -- the 64-row panels of the blocked
-            //  back-transformation, csrc/eigh_grid.hip, batched matrices of a few hundred rows: four times the workgroups)
+            break;
+        case NBX_GEMM_KERNEL_T32:
             launch<32, 32, 2, 2>(ctx, a_kc, b_kc, (int)m, (int)n, (int)k, alpha, A, lda, stride_a, B, ldb, stride_b,
                            beta, C, ldc, stride_c, nb, vec_a, vec_b, d_gate, gate_a, gate_b);
-        } else {
+            break;
+        default:
             launch<64, 64, 2, 2>(ctx, a_kc, b_kc, (int)m, (int)n, (int)k, alpha, A, lda, stride_a, B, ldb, stride_b,
                            beta, C, ldc, stride_c, nb, vec_a, vec_b, d_gate, gate_a, gate_b);
+            break;
         }
         NBX_LAUNCH_CHECK();
     }

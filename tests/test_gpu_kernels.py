@@ -90,6 +90,8 @@ def test_jk_dense_full_size_properties(be):
 @pytest.mark.parametrize("mnk", [(1, 1, 1), (7, 5, 3), (16, 16, 4), (33, 65, 17), (148, 148, 148), (128, 300, 148),
                                  (200, 40, 9)])
 def test_gemm(be, ta, tb, mnk):
+    """Every shape here has at most 512 tiles of 16 x 16 and k <= 4096: all of them, in all four layouts, run on
+    gemm_small_kernel.  The other kernels behind nbx_gemm are tested in tests/test_gpu_gemm.py."""
     m, n, k = mnk
     a = rnd(50, *((k, m) if ta == "T" else (m, k)))
     b = rnd(51, *((n, k) if tb == "T" else (k, n)))
@@ -118,7 +120,9 @@ def test_gemm_batched_alpha_beta(be):
 
 
 def test_gemm_large_tile_path(be):
-    m, n, k = 256, 4096, 148  # 128x128 tile configuration
+    """'T','N' at (256, 4096, 148): 64 tiles of 128 x 128 are too few for the 128 x 128 instance of gemm_f64_kernel
+    and for the DMA kernel, so this product runs on the 64 x 64 instance (tests/test_gpu_gemm.py reaches the others)."""
+    m, n, k = 256, 4096, 148
     a, b = rnd(55, k, m), rnd(56, k, n)
     got = be.to_host(be.gemm(be.asarray(a), be.asarray(b), "T", "N"))
     np.testing.assert_allclose(got, a.T @ b, rtol=0, atol=1e-11)
@@ -126,10 +130,17 @@ def test_gemm_large_tile_path(be):
 
 @pytest.mark.parametrize("mnk", [(256, 4096, 4), (130, 8190, 12), (200, 3000, 148), (128, 70000, 20), (66, 66 * 128, 2000)])
 def test_gemm_tn_lds_dma_kernel_edges(be, mnk):
-    """gemm_m4_tn_kernel ('T','N' operands, k-tiles by LDS-DMA, v_mfma_f64_4x4x4): a single 4-row step, a tile and a
-    half, edge tiles whose clamped loads bring columns nobody stores, a long k -- against numpy; batched with alpha and
-    beta; and the shapes it must hand back to the register-staged kernel (odd extents, k not a multiple of 4, k = 0)."""
+    """'T','N' products round the door of gemm_m4_tn_kernel (k-tiles by LDS-DMA, v_mfma_f64_4x4x4) against numpy.  Of
+    these shapes only (128, 70000, 20) has the 512 tiles of 128 x 128 that kernel is given (nbx_gemm_route is asked);
+    (256, 4096, 4), (130, 8190, 12), (200, 3000, 148) and (66, 8448, 2000) run on the 64 x 64 instance of
+    gemm_f64_kernel, and so do the batched alpha / beta product, the odd extents, k = 150 and k = 0 below.  The DMA
+    kernel's own edges (a single 4-row step, a last tile of one step, row and column edges, beta, batch strides, both
+    epilogues) are compared bit for bit in tests/test_gpu_gemm.py."""
     m, n, k = mnk
+    from nbed_amd import _nbx
+
+    dma = mnk == (128, 70000, 20)
+    assert (be.lib.nbx_gemm_route(b"T", b"N", m, n, k, 1, 1, 1) == _nbx.GEMM_KERNEL_TN_DMA) == dma
     a, b = rnd(57, k, m), rnd(58, k, n)
     got = be.to_host(be.gemm(be.asarray(a), be.asarray(b), "T", "N"))
     np.testing.assert_allclose(got, a.T @ b, rtol=0, atol=2e-13 * k)
