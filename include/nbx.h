@@ -205,6 +205,19 @@ size_t nbx_jk_packed_worksize(int64_t nao, int64_t p0, int64_t p1, int64_t ndm);
 int nbx_jk_packed(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_packed,
                   const double* d_dm, int64_t ndm, double* d_jk, void* d_work, size_t work_bytes);
 
+/* Test support: which file's kernel nbx_eri_pack / nbx_jk_packed serve a size with IN THIS PROCESS (the switches
+ * NBX_JK_M8 / NBX_JK_M4 / NBX_JK_MX are read once per process) and the instance size it runs as (nao itself, or the
+ * next instance with zero rows and columns; 0 with NBX_JK_KERNEL_NONE) -- the functions the launcher asks, host
+ * arithmetic only (no context, no GPU).  tests/jk_cases.py keeps a size per instance and tests/test_host_jk_cases.py
+ * fails when a size of the table moves to another kernel.                                                        */
+#define NBX_JK_KERNEL_NONE 0   /* not covered: nbx_jk_dense_sym */
+#define NBX_JK_KERNEL_S4 1     /* csrc/jk_s4.hip: the 4-fold tiles walked on the vector ALU */
+#define NBX_JK_KERNEL_M4 2     /* csrc/jk_m4.hip: 4-fold 4 x 4 blocks on the matrix cores (NBX_JK_M8=0) */
+#define NBX_JK_KERNEL_M8 3     /* csrc/jk_m8.hip: the 8-fold form, N = 97 .. 148 */
+#define NBX_JK_KERNEL_MX 4     /* csrc/jk_mx.hip: N = 149 .. 256 */
+#define NBX_JK_KERNEL_MX_HI 5  /* csrc/jk_mx_hi.hip: N = 257 .. 400 */
+int nbx_jk_packed_route(int64_t nao, int* kernel, int* run_as);
+
 /* nbx_jk_packed over the whole tensor (p0 = 0, p1 = N, two spin densities) with the Fock
  * assembly of nbx_fock_uhf done by its reduction kernel (one launch less per SCF cycle):
  *   d_hv : (2,N,N) hcore + V_emb;  d_fock[x] = d_hv[x] + J - K[x];  d_vhf[x] = J - K[x] (may be

@@ -30,6 +30,8 @@ XC_CODES = {"slater": 0, "lda": 1, "lda,vwn_rpa": 1, "lda,vwn": 2, "lda,vwn5": 2
 PROF_JK_DENSE, PROF_AO2MO_Q1, PROF_AO2MO, PROF_EIGH, PROF_SVD, PROF_GEMM = range(6)
 # nbx_gemm_route answers (NBX_GEMM_KERNEL_*)
 GEMM_KERNEL_NONE, GEMM_KERNEL_SMALL, GEMM_KERNEL_T32, GEMM_KERNEL_T64, GEMM_KERNEL_T128, GEMM_KERNEL_TN_DMA = range(6)
+# nbx_jk_packed_route answers (NBX_JK_KERNEL_*)
+JK_KERNEL_NONE, JK_KERNEL_S4, JK_KERNEL_M4, JK_KERNEL_M8, JK_KERNEL_MX, JK_KERNEL_MX_HI = range(6)
 
 
 class NbxError(RuntimeError):
@@ -93,6 +95,7 @@ SIGNATURES = {
     "nbx_jk_dense_sym_worksize": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "nbx_jk_packed_supported": (c_int, [c_int64]),
     "nbx_jk_packed_fold": (c_int, [c_int64]),
+    "nbx_jk_packed_route": (c_int, [c_int64, POINTER(c_int), POINTER(c_int)]),
     "nbx_eri_packed_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "nbx_eri_pack": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
     "nbx_jk_packed_worksize": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),

@@ -422,6 +422,33 @@ extern "C" int nbx_jk_packed_fold(int64_t nao) {
     return m8_padded(nao) ? 8 : 4;
 }
 
+// Test support (include/nbx.h): which file's kernel s4_jk hands nao to in this process and the instance size it runs as --
+// asked of the functions s4_jk, nbx_eri_pack and nbx_jk_packed_worksize ask, in their order.
+bool nbx_jk_mx_covers_hi(int64_t N);  // (jk_mx_hi.hip: the instances of the second translation unit)
+extern "C" int nbx_jk_packed_route(int64_t nao, int* kernel, int* run_as) {
+    if (kernel == nullptr || run_as == nullptr) return NBX_E_INVALID;
+    int k = NBX_JK_KERNEL_NONE;
+    int64_t n = 0;
+    if (const int64_t nx = mx_padded(nao)) {
+        k = nbx_jk_mx_covers_hi(nx) ? NBX_JK_KERNEL_MX_HI : NBX_JK_KERNEL_MX;
+        n = nx;
+    } else if (const int64_t np = s4_padded(nao)) {
+        if (const int64_t n8 = m8_padded(nao)) {
+            k = NBX_JK_KERNEL_M8;
+            n = n8;
+        } else if (const int64_t n4 = m4_padded(nao)) {
+            k = NBX_JK_KERNEL_M4;
+            n = n4;
+        } else {
+            k = NBX_JK_KERNEL_S4;
+            n = np;
+        }
+    }
+    *kernel = k;
+    *run_as = (int)n;
+    return NBX_OK;
+}
+
 extern "C" size_t nbx_eri_packed_bytes(int64_t nao, int64_t p0, int64_t p1) {
     if (p0 < 0 || p1 < p0 || p1 > nao) return 0;
     if (const int64_t nx = mx_padded(nao)) return nbx_jk_mx_packed_bytes(nx, p0, p1);

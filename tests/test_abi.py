@@ -166,6 +166,33 @@ def test_packed_sizes_are_host_arithmetic_and_additive_over_slabs():
     assert rows4[255] == 256 * rows4[0]
 
 
+def test_jk_packed_route_is_host_arithmetic_and_agrees_with_the_other_queries():
+    """nbx_jk_packed_route needs no GPU and no context; its answers agree with nbx_jk_packed_supported / _fold for every
+    size, and null pointers are refused."""
+    import ctypes
+
+    lib = _nbx.load_library()
+    kern, run_as = ctypes.c_int(), ctypes.c_int()
+    for n in range(-1, 420):
+        assert lib.nbx_jk_packed_route(n, ctypes.byref(kern), ctypes.byref(run_as)) == _nbx.NBX_OK
+        sup = lib.nbx_jk_packed_supported(n)
+        # (supported = 2 says "zero-padded" from jk_s4.hip's point of view: an even size jk_s4.hip has an instance for
+        #  answers 1 even where jk_m8.hip pads it to a multiple of four)
+        assert (sup == 0) == (kern.value == _nbx.JK_KERNEL_NONE) and (run_as.value != n or sup == 1 or n == 0), n
+        assert (run_as.value == 0) == (kern.value == _nbx.JK_KERNEL_NONE) and (run_as.value == 0 or n <= run_as.value <= n + 8), n
+        assert lib.nbx_jk_packed_fold(n) == {_nbx.JK_KERNEL_NONE: 0, _nbx.JK_KERNEL_M8: 8}.get(kern.value, 4), n
+        assert (lib.nbx_eri_packed_bytes(n, 0, n) > 0) == (kern.value != _nbx.JK_KERNEL_NONE), n
+    got = {}
+    for n in (15, 16, 96, 97, 148, 149, 256, 257, 264, 400, 401):
+        lib.nbx_jk_packed_route(n, ctypes.byref(kern), ctypes.byref(run_as))
+        got[n] = (kern.value, run_as.value)
+    s4, m8, mx, hi = _nbx.JK_KERNEL_S4, _nbx.JK_KERNEL_M8, _nbx.JK_KERNEL_MX, _nbx.JK_KERNEL_MX_HI
+    assert got == {15: (0, 0), 16: (s4, 24), 96: (s4, 96), 97: (m8, 100), 148: (m8, 148), 149: (mx, 152), 256: (mx, 256),
+                   257: (0, 0), 264: (hi, 272), 400: (hi, 400), 401: (0, 0)}
+    assert lib.nbx_jk_packed_route(148, None, ctypes.byref(run_as)) == _nbx.NBX_E_INVALID
+    assert lib.nbx_jk_packed_route(148, ctypes.byref(kern), None) == _nbx.NBX_E_INVALID
+
+
 def test_jk_m8_geometry(tmp_path):
     """The compile-time geometry of csrc/jk_m8.hip (the 8-fold packed tiles: chunks of whole block rows, tile lengths and
     addresses, ring / LDS / vmcnt budgets, the staging order of the Dtot' table and of the J partials and its identity with
