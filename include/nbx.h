@@ -677,7 +677,10 @@ int nbx_mu_cycle_fock_post(nbx_ctx* ctx, const nbx_huz_state* st, const double* 
  *   reduced against ao / dao in the epilogue (each array read once).  nao <= 640.
  * nbx_xc_functional:  energy density and first derivatives, written out analytically, of `code` (the semi-local part:
  *   NBX_XC_SLATER; _LDA_VWN_RPA = Slater + VWN(RPA); _LDA_VWN5 = Slater + VWN5, PySCF's default "lda,vwn"; _B3LYP =
- *   0.08 Slater + 0.72 B88 + 0.19 VWN(RPA) + 0.81 LYP, libxc's HYB_GGA_XC_B3LYP without its 0.2 exact exchange), d_w
+ *   0.08 Slater + 0.72 B88 + 0.19 VWN(RPA) + 0.81 LYP, libxc's HYB_GGA_XC_B3LYP without its 0.2 exact exchange;
+ *   _LDA_PW_MOD = Slater + Perdew-Wang 1992 (LDA_C_PW_MOD); _PBE = GGA_X_PBE + GGA_C_PBE; _PBEH = 0.75 GGA_X_PBE +
+ *   GGA_C_PBE, HYB_GGA_XC_PBEH ("PBE0", Gaussian's PBE1PBE) without its 0.25 exact exchange; _BLYP = Slater + B88 +
+ *   LYP; _B3LYP5 = _B3LYP with VWN5 in place of VWN(RPA), HYB_GGA_XC_B3LYP5), d_w
  *   (npts) the quadrature weights.  Densities are clamped from below at rho_floor / 2 and points with
  *   rho_a + rho_b <= rho_floor carry no weight.  Out: d_vr (2, npts) = w dE/drho_x; d_vec (2, 3, npts) =
  *   w (2 dE/dsigma_xx grad rho_x + dE/dsigma_ab grad rho_other); d_sums[0] = E_xc, d_sums[1] = the integrated
@@ -689,6 +692,11 @@ int nbx_mu_cycle_fock_post(nbx_ctx* ctx, const nbx_huz_state* st, const double* 
 #define NBX_XC_LDA_VWN_RPA 1
 #define NBX_XC_LDA_VWN5 2
 #define NBX_XC_B3LYP 3
+#define NBX_XC_LDA_PW_MOD 4
+#define NBX_XC_PBE 5
+#define NBX_XC_PBEH 6
+#define NBX_XC_BLYP 7
+#define NBX_XC_B3LYP5 8
 int nbx_xc_rho(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao, const double* d_dm,
                double* d_rho, double* d_grad);
 size_t nbx_xc_functional_worksize(int64_t npts);

@@ -25,7 +25,8 @@ NBX_E_UNSUPPORTED = -5
 LOC_PM, LOC_BOYS = 0, 1  # nbx_loc_worksize kinds (NBX_LOC_PM, NBX_LOC_BOYS)
 
 HUZ_JK_PACKED, HUZ_JK_SYM = 0, 1
-XC_CODES = {"slater": 0, "lda": 1, "lda,vwn_rpa": 1, "lda,vwn": 2, "lda,vwn5": 2, "svwn": 2, "b3lyp": 3}
+XC_CODES = {"slater": 0, "lda": 1, "lda,vwn_rpa": 1, "lda,vwn": 2, "lda,vwn5": 2, "svwn": 2, "b3lyp": 3, "lda,pw_mod": 4,
+            "pbe": 5, "pbe,pbe": 5, "pbeh": 6, "pbe1pbe": 6, "blyp": 7, "b3lyp5": 8}
 
 PROF_JK_DENSE, PROF_AO2MO_Q1, PROF_AO2MO, PROF_EIGH, PROF_SVD, PROF_GEMM = range(6)
 # nbx_gemm_route answers (NBX_GEMM_KERNEL_*)

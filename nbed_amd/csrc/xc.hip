@@ -10,8 +10,9 @@
 //   xc_functional_kernel  one thread per grid point: energy density and its first derivatives with respect to
 //                      (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb) written out analytically (Slater, Becke 88,
 //                      VWN-RPA / VWN5, LYP in Miehlich's form: libxc's B3LYP = 0.08 S + 0.72 B88 + 0.19 VWN_RPA +
-//                      0.81 LYP + 0.2 HF), quadrature weights folded in, E_xc and the electron count reduced in a
-//                      fixed order                                                                  -- ALU (exp, log, cbrt)
+//                      0.81 LYP + 0.2 HF, B3LYP5 with VWN5, BLYP; PBE exchange, Perdew-Wang 1992 and PBE
+//                      correlation: PBE, PBEH), one instantiation per functional, quadrature weights folded in, E_xc
+//                      and the electron count reduced in a fixed order                              -- ALU (exp, log, cbrt)
 //   xc_vmat_kernel     v[m][n] = sum_g ao[g][m] half[g][n],  half = v_rho / 2 ao + (2 v_ss grad rho_s + v_ab grad
 //                      rho_o) . dao, with `half` built ON THE FLY as the B operand (it never exists in memory), split
 //                      over chunks of grid points; xc_vmat_reduce_kernel adds the chunks in a fixed order and
@@ -253,16 +254,132 @@ __device__ __forceinline__ void xc_lyp(double s, double ra, double rb, double sa
     o.vab += s * abw * (ra * rb * 2.0 * (47.0 / 18.0 - 7.0 * delta / 18.0) - 4.0 / 3.0 * rho2);
 }
 
+// Perdew-Burke-Ernzerhof exchange for one spin channel (libxc GGA_X_PBE, spin-scaled): e = -cx rho^(4/3) F(p),
+// p = s^2 = sigma / (4 (6 pi^2)^(2/3) rho^(8/3)),  F = 1 + kappa - kappa / (1 + mu p / kappa) = 1 + kappa mu p / (kappa + mu p),
+// F' = kappa^2 mu / (kappa + mu p)^2;  de/drho = -(4/3) cx rho^(1/3) (F - 2 p F'),  de/dsigma = -cx F' / (4 (6 pi^2)^(2/3) rho^(4/3))
+__device__ __forceinline__ void xc_pbe_x(double s, double r, double sg, double& e, double& vr, double& vs) {
+    const double cx = 0.9305257363491002;   // (3/2) (3 / (4 pi))^(1/3)
+    const double c2 = 0.016455307846020558;  // 1 / (4 (6 pi^2)^(2/3))
+    const double kappa = 0.804, mu = 0.2195149727645171;  // mu = beta pi^2 / 3, beta = 0.06672455060314922
+    const double r13 = cbrt(r), r43 = r13 * r;
+    const double p = c2 * sg / (r43 * r43);
+    const double den = fma(mu, p, kappa);
+    const double F = 1.0 + kappa * mu * p / den;
+    const double dF = kappa * kappa * mu / (den * den);
+    e += s * (-cx * r43 * F);
+    vr += s * (-(4.0 / 3.0) * cx * r13 * (F - 2.0 * p * dF));
+    vs += s * (-cx * c2 * dF / r43);
+}
+
+// Perdew and Wang's G(rs) = -2 A (1 + a1 rs) ln(1 + 1 / Q),  Q = 2 A (b1 x + b2 x^2 + b3 x^3 + b4 x^4),  x = sqrt(rs),
+// and dG/drs = -2 A a1 ln(1 + 1 / Q) + 2 A (1 + a1 rs) Q' / (Q (Q + 1))
+__device__ __forceinline__ void xc_pw_g(double x, double a, double a1, double b1, double b2, double b3, double b4, double& g,
+                                        double& dg) {
+    const double q = 2.0 * a * x * fma(x, fma(x, fma(x, b4, b3), b2), b1);
+    const double dq = a * (b1 / x + fma(x, fma(4.0 * b4, x, 3.0 * b3), 2.0 * b2));
+    const double l = log1p(1.0 / q);
+    const double pre = -2.0 * a * fma(a1, x * x, 1.0);
+    g = pre * l;
+    dg = -2.0 * a * a1 * l - pre * dq / (q * (q + 1.0));
+}
+
+// The correlation energy per electron of Perdew and Wang 1992 with libxc's LDA_C_PW_MOD constants:
+//   eps = eps0 + alpha_c f(zeta) / f''(0) (1 - zeta^4) + (eps1 - eps0) f(zeta) zeta^4
+// with its derivatives with respect to rs and zeta, and what the gradient correction needs of the spin variables
+struct XcPw {
+    double rho, rs, up, dn, cp, cm;  // 1 +- zeta and their cube roots
+    double eps, drs, dz;
+};
+
+__device__ __forceinline__ XcPw xc_pw_eps(double ra, double rb) {
+    XcPw w;
+    w.rho = ra + rb;
+    const double zeta = (ra - rb) / w.rho;
+    const double x = sqrt(cbrt(0.238732414637843 / w.rho));  // sqrt(rs), rs = (3 / (4 pi rho))^(1/3)
+    w.rs = x * x;
+    w.up = 2.0 * ra / w.rho, w.dn = 2.0 * rb / w.rho;  // 1 +- zeta, never by subtraction: zeta -> +-1 when a spin is empty
+    w.cp = cbrt(w.up), w.cm = cbrt(w.dn);
+    const double c43 = 0.5198420997897464;   // 2^(4/3) - 2
+    const double fpp0 = 1.7099209341613657;  // 4 / (9 (2^(1/3) - 1)), exact
+    const double fz = (w.cp * w.up + w.cm * w.dn - 2.0) / c43;
+    const double dfz = (4.0 / 3.0) * (w.cp - w.cm) / c43;
+    double e0, de0, e1, de1, ma, dma;  // ma = -alpha_c
+    xc_pw_g(x, 0.0310907, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294, e0, de0);
+    xc_pw_g(x, 0.01554535, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517, e1, de1);
+    xc_pw_g(x, 0.0168869, 0.11125, 10.357, 3.6231, 0.88026, 0.49671, ma, dma);
+    const double z3 = zeta * zeta * zeta, z4 = z3 * zeta;
+    const double omz4 = w.up * w.dn * fma(zeta, zeta, 1.0);  // 1 - zeta^4 as a product of its factors
+    w.eps = e0 - ma * fz / fpp0 * omz4 + (e1 - e0) * fz * z4;
+    w.drs = de0 - dma * fz / fpp0 * omz4 + (de1 - de0) * fz * z4;
+    w.dz = -ma / fpp0 * (dfz * omz4 - 4.0 * fz * z3) + (e1 - e0) * (dfz * z4 + 4.0 * fz * z3);
+    return w;
+}
+
+// e = rho eps(rs, zeta):  d/d rho_s = eps - (rs / 3) d eps / d rs  +-  (1 -+ zeta) d eps / d zeta
+__device__ __forceinline__ void xc_pw_mod(double s, double ra, double rb, XcDer& o) {
+    const XcPw w = xc_pw_eps(ra, rb);
+    const double common = w.eps - (w.rs / 3.0) * w.drs;
+    o.e += s * w.rho * w.eps;
+    o.va += s * (common + w.dn * w.dz);
+    o.vb += s * (common - w.up * w.dz);
+}
+
+// Perdew-Burke-Ernzerhof correlation (libxc GGA_C_PBE): e = rho (eps + H),
+//   H = gamma phi^3 ln(1 + X),  X = (beta / gamma) T (1 + y) / (1 + y + y^2),  y = A T,  A = (beta / gamma) / em,
+//   em = exp(u) - 1,  u = -eps / (gamma phi^3),  phi = ((1 + zeta)^(2/3) + (1 - zeta)^(2/3)) / 2,
+//   T = t^2 = sigma / (4 phi^2 k_s^2 rho^2) = pi sigma / (16 (3 pi^2)^(1/3) phi^2 rho^(7/3))
+// X = em (y + y^2) / (1 + y + y^2) = em (1 - 1 / (1 + y + y^2)): the second form where y > 1 (y reaches 1e7 at a large
+// reduced gradient, where H -> -eps).  With D = 1 + y + y^2:
+//   dX/dT (A fixed) = (beta / gamma) (1 + 2 y) / D^2,   dX/du (T fixed) = y^3 (2 + y) (1 + em) / D^2,
+//   dH = 3 gamma phi^2 ln(1 + X) dphi + gamma phi^3 / (1 + X) dX,
+//   du = -d eps / (gamma phi^3) - 3 u dphi / phi,   dT = T (d sigma / sigma - 2 dphi / phi - (7/3) d rho / rho)
+// expm1 and log1p: eps -> 0 in the density tails.  dphi/dzeta = ((1 + zeta)^(-1/3) - (1 - zeta)^(-1/3)) / 3 is finite
+// because the densities are clamped at rho_floor / 2.
+__device__ __forceinline__ void xc_pbe_c(double s, double ra, double rb, double saa, double sab, double sbb, XcDer& o) {
+    const double gamma = 0.031090690869654895;  // (1 - ln 2) / pi^2
+    const double bg = 2.1461263399673646;       // beta / gamma, beta = 0.06672455060314922
+    const double ct = 0.0634682060977037;       // pi / (16 (3 pi^2)^(1/3))
+    const XcPw w = xc_pw_eps(ra, rb);
+    const double phi = 0.5 * (w.cp * w.cp + w.cm * w.cm);
+    const double dphi = (1.0 / w.cp - 1.0 / w.cm) / 3.0;
+    const double phi2 = phi * phi, g3 = gamma * phi2 * phi;
+    const double kt = ct / (phi2 * w.rho * w.rho * cbrt(w.rho));  // T = kt sigma
+    const double T = kt * (saa + 2.0 * sab + sbb);
+    const double em = expm1(-w.eps / g3);
+    const double y = bg / em * T;
+    const double D = fma(y, y + 1.0, 1.0), D2 = D * D;
+    const double X = em * (y > 1.0 ? 1.0 - 1.0 / D : y * (1.0 + y) / D);
+    const double L = log1p(X);
+    const double H = g3 * L;
+    const double hx = g3 / (1.0 + X);                              // dH/dX
+    const double XT = bg * fma(2.0, y, 1.0) / D2;                  // dX/dT
+    const double q = y * y * y * (2.0 + y) * (1.0 + em) / D2 / (1.0 + X);  // (dH/dX) (dX/du) / (gamma phi^3)
+    const double vs = w.rho * hx * XT * kt;                        // d(rho H) / d sigma
+    // d(rho H)/d rho at fixed zeta (d eps / d rho = -(rs / (3 rho)) d eps / d rs), and dH/dzeta (gamma phi^3 u = -eps)
+    const double Hn = H - (7.0 / 3.0) * hx * XT * T + q * w.rs * w.drs / 3.0;
+    const double Hz = (3.0 * gamma * phi2 * L - 2.0 * hx * XT * T / phi + 3.0 * q * w.eps / phi) * dphi - q * w.dz;
+    const double common = w.eps - (w.rs / 3.0) * w.drs + Hn;
+    const double dz = w.dz + Hz;
+    o.e += s * w.rho * (w.eps + H);
+    o.va += s * (common + w.dn * dz);
+    o.vb += s * (common - w.up * dz);
+    o.vaa += s * vs;
+    o.vab += s * 2.0 * vs;
+    o.vbb += s * vs;
+}
+
 constexpr int XC_FN_THREADS = 256;
 
-// code: NBX_XC_SLATER / _LDA_VWN_RPA / _LDA_VWN5 / _B3LYP (the semi-local part; the exact-exchange fraction is the
-// caller's).  Conventions of nbed_amd.xc.XCProvider.__call__ (the torch expression this kernel replaces): densities
-// clamped from below at rho_floor / 2, sigma_aa and sigma_bb lifted by 1e-40, points with rho_a + rho_b <= rho_floor
-// dropped; outputs carry the quadrature weights:
+// CODE: NBX_XC_SLATER / _LDA_VWN_RPA / _LDA_VWN5 / _B3LYP / _LDA_PW_MOD / _PBE / _PBEH / _BLYP / _B3LYP5 (the semi-local
+// part; the exact-exchange fraction is the caller's), one instantiation each: a kernel holding every branch would
+// charge the registers of PBE correlation to the LDA codes.  Conventions of nbed_amd.xc.XCProvider.__call__ (the torch
+// expression this kernel replaces): densities clamped from below at rho_floor / 2, sigma_aa and sigma_bb lifted by
+// 1e-40, points with rho_a + rho_b <= rho_floor dropped; outputs carry the quadrature weights:
 //   vr[x][g]     = w keep dE/drho_x
 //   vec[x][a][g] = w keep (2 dE/dsigma_xx grad rho_x + dE/dsigma_ab grad rho_other)[a]
 //   part[blk]    = (sum w keep e, sum w (rho_a + rho_b)) of the block
-__global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_kernel(int code, int64_t npts, const double* __restrict__ rho,
+template <int CODE>
+__global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_kernel(int64_t npts, const double* __restrict__ rho,
                                                                       const double* __restrict__ grad,
                                                                       const double* __restrict__ w, double rho_floor,
                                                                       double* __restrict__ vr, double* __restrict__ vec,
@@ -281,20 +398,33 @@ __global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_kernel(int code, 
         const double sbb = fma(gbx, gbx, fma(gby, gby, gbz * gbz)) + 1.0e-40;
         const double sab = fma(gax, gbx, fma(gay, gby, gaz * gbz));
         XcDer o = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (code == NBX_XC_SLATER) {
+        if (CODE == NBX_XC_SLATER) {
             xc_slater(1.0, ra, rb, o);
-        } else if (code == NBX_XC_LDA_VWN_RPA) {
+        } else if (CODE == NBX_XC_LDA_VWN_RPA) {
             xc_slater(1.0, ra, rb, o);
             xc_vwn<true>(1.0, ra, rb, o);
-        } else if (code == NBX_XC_LDA_VWN5) {
+        } else if (CODE == NBX_XC_LDA_VWN5) {
             xc_slater(1.0, ra, rb, o);
             xc_vwn<false>(1.0, ra, rb, o);
-        } else {  // B3LYP
+        } else if (CODE == NBX_XC_B3LYP || CODE == NBX_XC_B3LYP5) {
             xc_slater(0.8, ra, rb, o);
             xc_b88(0.72, ra, saa, o.e, o.va, o.vaa);
             xc_b88(0.72, rb, sbb, o.e, o.vb, o.vbb);
-            xc_vwn<true>(0.19, ra, rb, o);
+            xc_vwn<CODE == NBX_XC_B3LYP>(0.19, ra, rb, o);
             xc_lyp(0.81, ra, rb, saa, sab, sbb, o);
+        } else if (CODE == NBX_XC_LDA_PW_MOD) {
+            xc_slater(1.0, ra, rb, o);
+            xc_pw_mod(1.0, ra, rb, o);
+        } else if (CODE == NBX_XC_PBE || CODE == NBX_XC_PBEH) {
+            const double ax = CODE == NBX_XC_PBE ? 1.0 : 0.75;
+            xc_pbe_x(ax, ra, saa, o.e, o.va, o.vaa);
+            xc_pbe_x(ax, rb, sbb, o.e, o.vb, o.vbb);
+            xc_pbe_c(1.0, ra, rb, saa, sab, sbb, o);
+        } else {  // BLYP
+            xc_slater(1.0, ra, rb, o);
+            xc_b88(1.0, ra, saa, o.e, o.va, o.vaa);
+            xc_b88(1.0, rb, sbb, o.e, o.vb, o.vbb);
+            xc_lyp(1.0, ra, rb, saa, sab, sbb, o);
         }
         const double wk = wg * keep;
         e_w = wk * o.e;
@@ -483,14 +613,29 @@ extern "C" int nbx_xc_functional(nbx_ctx* ctx, int code, int64_t npts, const dou
                                  const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
                                  size_t work_bytes) {
     NBX_CHECK_ARG(ctx && d_rho && d_grad && d_w && d_vr && d_vec && d_sums && d_work && npts >= 0);
-    NBX_CHECK_ARG(code == NBX_XC_SLATER || code == NBX_XC_LDA_VWN_RPA || code == NBX_XC_LDA_VWN5 || code == NBX_XC_B3LYP);
+    NBX_CHECK_ARG(code >= NBX_XC_SLATER && code <= NBX_XC_B3LYP5);
     NBX_CHECK_ARG(rho_floor > 0.0 && work_bytes >= nbx_xc_functional_worksize(npts));
     if (npts == 0) return nbx_memset(ctx, d_sums, 0, 2 * sizeof(double));
     const int64_t nblk = nbx_cdiv(npts, XC_FN_THREADS);
     NBX_CHECK_ARG(nblk < (1ll << 30));
     double* part = static_cast<double*>(d_work);
-    hipLaunchKernelGGL(xc_functional_kernel, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, code, npts, d_rho,
-                       d_grad, d_w, rho_floor, d_vr, d_vec, part);
+#define NBX_XC_FN(CODE_)                                                                                                  \
+    case CODE_:                                                                                                           \
+        hipLaunchKernelGGL(xc_functional_kernel<CODE_>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,  \
+                           d_rho, d_grad, d_w, rho_floor, d_vr, d_vec, part);                                             \
+        break
+    switch (code) {
+        NBX_XC_FN(NBX_XC_SLATER);
+        NBX_XC_FN(NBX_XC_LDA_VWN_RPA);
+        NBX_XC_FN(NBX_XC_LDA_VWN5);
+        NBX_XC_FN(NBX_XC_B3LYP);
+        NBX_XC_FN(NBX_XC_LDA_PW_MOD);
+        NBX_XC_FN(NBX_XC_PBE);
+        NBX_XC_FN(NBX_XC_PBEH);
+        NBX_XC_FN(NBX_XC_BLYP);
+        default: NBX_XC_FN(NBX_XC_B3LYP5);
+    }
+#undef NBX_XC_FN
     NBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(xc_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, (int)nblk, part, d_sums);
     NBX_LAUNCH_CHECK();

@@ -127,8 +127,10 @@ class _TaggedVeff(np.ndarray):
 class BuiltinHFProvider:
     """The out-of-path pieces without PySCF, for what ``nbed_amd.integrals`` and ``nbed_amd.xc``
     cover: molecules of H, C, N, O (F) in STO-3G, 6-31G, 6-31G* or cc-pVDZ with ``xc_functional`` = 'b3lyp' (the reference's
-    default workflow: global B3LYP Kohn-Sham, nbed/driver.py:155-191), 'lda' or 'hf' (exact exchange:
-    HF-in-HF embedding; PySCF's ``dft.UKS`` accepts the same strings).  Integrals come from the
+    default workflow: global B3LYP Kohn-Sham, nbed/driver.py:155-191), 'b3lyp5', 'blyp', 'pbe', 'pbeh' / 'pbe1pbe'
+    (the functional also called PBE0; that spelling is not accepted), 'lda', 'lda,vwn', 'lda,pw_mod' or 'hf' (exact
+    exchange: HF-in-HF embedding) -- the names of ``nbed_amd.xc.HYBRID_FRACTION``; PySCF's ``dft.UKS`` accepts the same
+    strings.  Integrals come from the
     host-side McMurchie-Davidson engine, exchange-correlation from the host-side quadrature
     (``XCProvider``), Coulomb and exact exchange from libnbx (``GpuUKS`` / ``GpuUHF``)."""
 
@@ -255,8 +257,11 @@ class BuiltinHFProvider:
         from .scf import GpuUHF
 
         if run_qmmm or not self.supports(config):
-            raise NbedDriverError("BuiltinHFProvider covers xc_functional in ('b3lyp', 'lda', 'hf'), H/C/N/O in "
-                                  "STO-3G, 6-31G(*), cc-pVDZ, no QM/MM")
+            from . import xc as xcmod
+
+            raise NbedDriverError(f"BuiltinHFProvider covers xc_functional in {sorted(xcmod.HYBRID_FRACTION)} ('pbeh' / "
+                                  "'pbe1pbe' is the functional also called PBE0), H/C/N/O in STO-3G, 6-31G(*), cc-pVDZ, "
+                                  "no QM/MM")
         if str(config.xc_functional).lower() != "hf":
             ks = self._uks(config, self.build_mol(config), config.xc_functional, self._be)
             ks.conv_tol = config.convergence

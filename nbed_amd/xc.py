@@ -15,6 +15,13 @@ Functionals (libxc definitions, spin-polarised):
   * ``b3lyp``  0.08 Slater + 0.72 B88 + 0.19 VWN(RPA) + 0.81 LYP + 0.20 HF  (libxc XC_HYB_GGA_XC_B3LYP,
                what PySCF >= 2.3 means by "b3lyp": the warning captured in
                docs/source/notebooks/localization.ipynb cell 13)
+  * ``lda,pw_mod`` Slater exchange + Perdew-Wang 1992 correlation (libxc LDA_C_PW_MOD: the local part of PBE)
+  * ``pbe``    PBE exchange + PBE correlation (libxc GGA_X_PBE + GGA_C_PBE; also spelt ``pbe,pbe``)
+  * ``pbeh``   0.75 PBE exchange + PBE correlation + 0.25 HF (libxc HYB_GGA_XC_PBEH; Gaussian's ``pbe1pbe``, the
+               functional also known as PBE0 -- that spelling is not an alias yet)
+  * ``blyp``   Slater + B88 + LYP
+  * ``b3lyp5`` 0.08 Slater + 0.72 B88 + 0.19 VWN5 + 0.81 LYP + 0.20 HF (libxc HYB_GGA_XC_B3LYP5: B3LYP with the
+               Ceperley-Alder fit in place of VWN(RPA))
   * ``hf``     no semi-local part, 100 % exact exchange
 Energy densities are written once, in torch float64; their derivatives with respect to
 (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb) come from autograd, not from hand-derived formulas.
@@ -45,7 +52,8 @@ def _torch():
 BRAGG = {"H": 0.35, "C": 0.70, "N": 0.65, "O": 0.60, "F": 0.50}
 
 HYBRID_FRACTION = {"hf": 1.0, "b3lyp": 0.2, "lda": 0.0, "lda,vwn_rpa": 0.0, "lda,vwn": 0.0, "lda,vwn5": 0.0, "svwn": 0.0,
-                   "slater": 0.0}
+                   "slater": 0.0, "lda,pw_mod": 0.0, "pbe": 0.0, "pbe,pbe": 0.0, "pbeh": 0.25, "pbe1pbe": 0.25, "blyp": 0.0,
+                   "b3lyp5": 0.2}
 
 
 def hybrid_fraction(xc: str) -> float:
@@ -407,6 +415,75 @@ def _lyp(t, ra, rb, saa, sab, sbb):
     return t1 - a * b * omega * brace
 
 
+_PBE_BETA = 0.06672455060314922  # libxc's beta of PBE: mu = beta pi^2 / 3 = 0.2195149727645171
+_PBE_GAMMA = (1.0 - math.log(2.0)) / math.pi**2
+
+
+def _pbe_x(t, ra, rb, saa, sbb):
+    """Perdew-Burke-Ernzerhof exchange (libxc GGA_X_PBE), spin-scaled: per channel -cx rho^(4/3) F(s^2) with
+    s^2 = sigma / (4 (6 pi^2)^(2/3) rho^(8/3)) and F = 1 + kappa - kappa / (1 + mu s^2 / kappa), written as
+    1 + kappa mu s^2 / (kappa + mu s^2).  Contains the Slater exchange (F(0) = 1)."""
+    cx = 1.5 * (3.0 / (4.0 * math.pi)) ** (1.0 / 3.0)
+    kappa, mu = 0.804, _PBE_BETA * math.pi**2 / 3.0
+    c2 = 0.25 / (6.0 * math.pi**2) ** (2.0 / 3.0)
+    out = 0.0
+    for r, s in ((ra, saa), (rb, sbb)):
+        r13 = r ** (1.0 / 3.0)
+        r43 = r13 * r
+        p = c2 * s / (r43 * r43)
+        out = out - cx * r43 * (1.0 + kappa * mu * p / (kappa + mu * p))
+    return out
+
+
+def _pw_eps(t, ra, rb):
+    """Perdew and Wang's 1992 correlation energy per electron eps(r_s, zeta) with libxc's LDA_C_PW_MOD constants
+    (f''(0) exact); returns (rho, eps, 1 + zeta, 1 - zeta)."""
+    rho = ra + rb
+    zeta = (ra - rb) / rho
+    up, dn = 2.0 * ra / rho, 2.0 * rb / rho  # 1 +- zeta, never by subtraction: zeta -> +-1 when a spin is empty
+    x = ((3.0 / (4.0 * math.pi)) / rho) ** (1.0 / 6.0)  # sqrt(rs)
+
+    def g(a, a1, b1, b2, b3, b4):
+        q1 = 2.0 * a * x * (b1 + x * (b2 + x * (b3 + x * b4)))
+        return -2.0 * a * (1.0 + a1 * x * x) * t.log1p(1.0 / q1)
+
+    e0 = g(0.0310907, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294)
+    e1 = g(0.01554535, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517)
+    mac = g(0.0168869, 0.11125, 10.357, 3.6231, 0.88026, 0.49671)  # -alpha_c
+    fz = (up ** (4.0 / 3.0) + dn ** (4.0 / 3.0) - 2.0) / (2.0 ** (4.0 / 3.0) - 2.0)
+    fpp0 = 4.0 / (9.0 * (2.0 ** (1.0 / 3.0) - 1.0))
+    z4 = zeta**4
+    omz4 = up * dn * (1.0 + zeta * zeta)  # 1 - zeta^4 as a product of its factors
+    return rho, e0 - mac * fz / fpp0 * omz4 + (e1 - e0) * fz * z4, up, dn
+
+
+def _pw_mod(t, ra, rb):
+    """Perdew-Wang 1992 correlation (libxc LDA_C_PW_MOD): e = rho eps(r_s, zeta)."""
+    rho, eps, _, _ = _pw_eps(t, ra, rb)
+    return rho * eps
+
+
+def _pbe_c(t, ra, rb, saa, sab, sbb):
+    """Perdew-Burke-Ernzerhof correlation (libxc GGA_C_PBE): e = rho (eps_PW + H),
+    H = gamma phi^3 ln(1 + (beta / gamma) t^2 (1 + y) / (1 + y + y^2)), y = A t^2,
+    A = (beta / gamma) / (exp(-eps / (gamma phi^3)) - 1).  expm1 and log1p: eps -> 0 in the density tails."""
+    rho, eps, up, dn = _pw_eps(t, ra, rb)
+    bg = _PBE_BETA / _PBE_GAMMA
+    phi = 0.5 * (up ** (2.0 / 3.0) + dn ** (2.0 / 3.0))
+    g3 = _PBE_GAMMA * phi**3
+    # t^2 = sigma / (4 phi^2 k_s^2 rho^2), k_s^2 = 4 k_F / pi, k_F = (3 pi^2 rho)^(1/3)
+    ct = math.pi / (16.0 * (3.0 * math.pi**2) ** (1.0 / 3.0))
+    tt = ct * (saa + 2.0 * sab + sbb) / (phi * phi * rho ** (7.0 / 3.0))
+    em = t.expm1(-eps / g3)  # beta / (gamma A)
+    y = bg * tt / em
+    # (beta / gamma) t^2 (1 + y) / (1 + y + y^2) = em (y + y^2) / (1 + y + y^2) = em (1 - 1 / (1 + y + y^2)).  Differentiated
+    # term by term, the quotients cancel to 1 / y^2 of their terms at a large reduced gradient (y reaches 1e7) and the
+    # last form loses y itself when y is small: each is used where its derivative is a sum of like terms
+    den = 1.0 + y + y * y
+    frac = t.where(y > 1.0, 1.0 - 1.0 / den, (y + y * y) / den)
+    return rho * (eps + g3 * t.log1p(em * frac))
+
+
 def energy_density(xc: str, ra, rb, saa, sab, sbb):
     """Semi-local exchange-correlation energy per volume (torch tensors); None for ``hf``."""
     t = _torch()
@@ -422,6 +499,17 @@ def energy_density(xc: str, ra, rb, saa, sab, sbb):
     if key == "b3lyp":
         return (0.8 * _slater(t, ra, rb) + 0.72 * _b88_correction(t, ra, rb, saa, sbb)
                 + 0.19 * _vwn_rpa(t, ra, rb) + 0.81 * _lyp(t, ra, rb, saa, sab, sbb))
+    if key == "lda,pw_mod":
+        return _slater(t, ra, rb) + _pw_mod(t, ra, rb)
+    if key in ("pbe", "pbe,pbe"):
+        return _pbe_x(t, ra, rb, saa, sbb) + _pbe_c(t, ra, rb, saa, sab, sbb)
+    if key in ("pbeh", "pbe1pbe"):
+        return 0.75 * _pbe_x(t, ra, rb, saa, sbb) + _pbe_c(t, ra, rb, saa, sab, sbb)
+    if key == "blyp":
+        return _slater(t, ra, rb) + _b88_correction(t, ra, rb, saa, sbb) + _lyp(t, ra, rb, saa, sab, sbb)
+    if key == "b3lyp5":
+        return (0.8 * _slater(t, ra, rb) + 0.72 * _b88_correction(t, ra, rb, saa, sbb)
+                + 0.19 * _vwn5(t, ra, rb) + 0.81 * _lyp(t, ra, rb, saa, sab, sbb))
     raise ValueError(f"functional {xc!r} is not in nbed_amd.xc")
 
 
