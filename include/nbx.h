@@ -108,6 +108,7 @@ int nbx_df_synth(nbx_ctx* ctx, int64_t nao, int64_t l0, int64_t l1, uint64_t see
 #define NBX_PROF_SVD 4         /* svd_jacobi_kernel                                          */
 #define NBX_PROF_GEMM 5        /* every gemm_f64_kernel launch                               */
 #define NBX_PROF_LOC 6         /* loc_pm_kernel / loc_boys_kernel                            */
+/* (7 = NBX_PROF_ERI: the class launches of nbx_eri_device, read with nbx_eri_class_ms)                  */
 /* on = 0: off; on = 1: every slot; on = 2 | (mask << 2): only the slots whose bit is set in
  * mask (an event pair costs a few microseconds of stream time, which matters inside an SCF
  * cycle: bench.py brackets the J/K kernel only).                                             */
@@ -774,6 +775,37 @@ int nbx_host_1e(int nshell, const int* ang, const int* nprim, const int* nfunc, 
  * the y and z overlap factors.                                                                        */
 int nbx_host_dipole(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
                     const double* exps, const double* coefs, const double* sph, int nthreads, double* r_out);
+
+/* ------------------------------------------------------------------ AO integrals of a real molecule (DEVICE)
+ * The same tensor as nbx_host_eri, dense (nao, nao, nao, nao), written into DEVICE memory by csrc/eri.hip: the
+ * producer the reference reaches through PySCF/libcint (gto.Mole.intor("int2e"), implied by
+ * scf.UKS(mol).kernel() at nbed/driver.py:155-191 and ao2mo at nbed/ham_builder.py:139-170), without the host
+ * tensor and its upload.  The shell arguments are nbx_host_eri's HOST arrays; pair data, primitive screening
+ * (cutoff * 1e-4) and the Schwarz test are the host engine's own code (csrc/ints_md.h), so both engines skip the
+ * same quartets and differ only in rounding.  Shells of angular momentum <= 2 (NBX_E_INVALID for l = 3: f shells
+ * stay on nbx_host_eri, and wherever nbx_host_eri refuses the shells).
+ *   out_device   nao^4 doubles; zeroed and filled on the context's stream (one launch per non-empty class
+ *                (la + lb, lc + ld), no atomics: two calls give the same bits).  The call returns once the pair
+ *                data and quartet lists have left host memory; the launches are queued behind them.
+ * While profiling is enabled for NBX_PROF_ERI every class launch is bracketed by HIP events;
+ * nbx_eri_class_ms waits for those of the last call and returns milliseconds per class (index 5 (la + lb) +
+ * (lc + ld), 0 for an empty class).                                                                          */
+#define NBX_PROF_ERI 7
+#define NBX_ERI_CLASSES 25
+int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                   const double* exps, const double* coefs, const double* sph, double cutoff, double* out_device);
+int nbx_eri_class_ms(nbx_ctx* ctx, double* ms_out);
+/* Test support and launch geometry of nbx_eri_device -- the function its launcher asks, host arithmetic only (no
+ * context, no GPU; the intor("int2e") call of nbed/driver.py:155-191 has no counterpart of it).  Per class
+ * (index 5 (la + lb) + (lc + ld), NBX_ERI_CLASSES entries each):
+ *   counts_out      canonical shell quartets (kl <= ij) that pass the Schwarz test; 0 = nothing is launched
+ *   lds_bytes_out   static LDS of one workgroup of the class's kernel
+ *   block_out       threads per workgroup (one wavefront, which owns one quartet at a time)
+ *   grid_out        workgroups launched (they stride over the class's list)
+ * NBX_E_INVALID exactly where nbx_eri_device returns it.                                                      */
+int nbx_eri_plan(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                 const double* exps, const double* coefs, const double* sph, double cutoff, int64_t* counts_out,
+                 int* lds_bytes_out, int* block_out, int64_t* grid_out);
 
 /* ------------------------------------------------------------------ coupled cluster (csrc/ccsd.hip)
  * What surrounds the GEMMs of a spin-orbital CCSD (nbed_amd/ccsd_gpu.py): the reference runs PySCF's

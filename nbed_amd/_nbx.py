@@ -29,6 +29,8 @@ XC_CODES = {"slater": 0, "lda": 1, "lda,vwn_rpa": 1, "lda,vwn": 2, "lda,vwn5": 2
             "pbe": 5, "pbe,pbe": 5, "pbeh": 6, "pbe1pbe": 6, "blyp": 7, "b3lyp5": 8}
 
 PROF_JK_DENSE, PROF_AO2MO_Q1, PROF_AO2MO, PROF_EIGH, PROF_SVD, PROF_GEMM = range(6)
+PROF_ERI = 7  # the class launches of nbx_eri_device (nbx_eri_class_ms)
+ERI_CLASSES = 25  # (la + lb, lc + ld), index 5 l_ab + l_cd
 # nbx_gemm_route answers (NBX_GEMM_KERNEL_*)
 GEMM_KERNEL_NONE, GEMM_KERNEL_SMALL, GEMM_KERNEL_T32, GEMM_KERNEL_T64, GEMM_KERNEL_T128, GEMM_KERNEL_TN_DMA = range(6)
 # nbx_jk_packed_route answers (NBX_JK_KERNEL_*)
@@ -185,6 +187,10 @@ SIGNATURES = {
     "nbx_host_1e": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, _P]),
     "nbx_host_eri": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_double, c_int, _P]),
     "nbx_host_dipole": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "nbx_eri_device": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_double, _P]),
+    "nbx_eri_class_ms": (c_int, [_P, POINTER(c_double)]),
+    "nbx_eri_plan": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_double, POINTER(c_int64), POINTER(c_int), POINTER(c_int),
+                             POINTER(c_int64)]),
     "nbx_huz_cycle": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                               c_int, _P, _P]),
     "nbx_huz_cycle_jk": (c_int, [_P, POINTER(HuzState), _P]),

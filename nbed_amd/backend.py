@@ -514,6 +514,27 @@ class HipBackend:
         self._call("nbx_synth_eri", nao, p0, p1, seed, self._p(out))
         return out
 
+    # ------------------------------------------------------------------ AO integrals of a real molecule
+    def eri(self, basis, cutoff: float = 1e-16):
+        """(pq|rs) of ``basis`` (``nbed_amd.integrals.Basis``, shells of l <= 2) as a device tensor (nao,)*4
+        (nbx_eri_device): zeroed and filled on this backend's stream, no host copy."""
+        from .integrals import _shell_arrays, max_ang
+
+        if max_ang(basis) > 2:
+            raise _nbx.NbxError(_nbx.NBX_E_INVALID, "the device integral engine covers shells of l <= 2 (s, p, d); "
+                                "f shells are the host engine's (integrals.two_electron_native)")
+        arrays = _shell_arrays(basis)
+        out = self.empty((basis.nao,) * 4)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        self._call("nbx_eri_device", len(basis.shells), *(ptr(a) for a in arrays), float(cutoff), self._p(out))
+        return out
+
+    def eri_class_ms(self) -> np.ndarray:
+        """Milliseconds of each class launch (5, 5) of the last ``eri`` call made under ``profile(slots=[PROF_ERI])``."""
+        ms = (c_double * _nbx.ERI_CLASSES)()
+        self._call("nbx_eri_class_ms", ms)
+        return np.array(ms[:]).reshape(5, 5)
+
     # ------------------------------------------------------------------ J/K
     def jk(self, eri, dm, p0: int = 0, p1: int | None = None):
         """(1+ndm, p1-p0, N): J rows from sum(dm), then K rows per dm (nbx_jk_dense)."""

@@ -124,18 +124,44 @@ class _TaggedVeff(np.ndarray):
     """ndarray carrying .ecoul / .exc like PySCF's tagged Kohn-Sham veff."""
 
 
+# Which engine ``eri_engine="auto"`` takes where both can serve (a backend with ``eri``, shells of l <= 2), decided by
+# tools/time_eri.py on an MI355X (profiles/eri_device/, DESIGN.md section 12): at octane / 6-31G* (N = 148) the device route
+# takes 73 ms against 543 ms of the host engine on 16 threads + upload.  Below about 40 functions the order is reversed
+# (the class launches follow one another, each as long as its longest quartet: ethane, 40 functions, 8.0 against 7.3 ms;
+# water / cc-pVDZ, 24 functions, 20 against 3 ms; propane, 58 functions, 10 against 25 ms), so ``auto`` keeps small molecules
+# on the host.
+AUTO_ERI_ON_DEVICE = True
+AUTO_ERI_MIN_NAO = 48
+
+
+class _DeviceRouteIntegrals(dict):
+    """``molecule_integrals(engine="native-1e")`` of the device route: holds no ``"eri"``; ``d["eri"]`` hands out a host
+    copy made on the spot (``fetch_eri``) and does not keep it, so ``"eri" in d`` stays False."""
+
+    fetch_eri = None
+
+    def __missing__(self, key):
+        if key == "eri" and self.fetch_eri is not None:
+            return self.fetch_eri()
+        raise KeyError(key)
+
+
 class BuiltinHFProvider:
     """The out-of-path pieces without PySCF, for what ``nbed_amd.integrals`` and ``nbed_amd.xc``
     cover: molecules of H, C, N, O (F) in STO-3G, 6-31G, 6-31G* or cc-pVDZ with ``xc_functional`` = 'b3lyp' (the reference's
     default workflow: global B3LYP Kohn-Sham, nbed/driver.py:155-191), 'b3lyp5', 'blyp', 'pbe', 'pbeh' / 'pbe1pbe'
     (the functional also called PBE0; that spelling is not accepted), 'lda', 'lda,vwn', 'lda,pw_mod' or 'hf' (exact
     exchange: HF-in-HF embedding) -- the names of ``nbed_amd.xc.HYBRID_FRACTION``; PySCF's ``dft.UKS`` accepts the same
-    strings.  Integrals come from the
-    host-side McMurchie-Davidson engine, exchange-correlation from the host-side quadrature
+    strings.  One-electron integrals come from the
+    host-side McMurchie-Davidson engine, (pq|rs) from it or from the same scheme on the device (``eri_engine``),
+    exchange-correlation from the host-side quadrature
     (``XCProvider``), Coulomb and exact exchange from libnbx (``GpuUKS`` / ``GpuUHF``)."""
 
-    def __init__(self, backend=None, xc_grid: tuple[int, int] | None = None):
-        """``xc_grid``: (radial points per heavy atom, polar angles) of the exchange-correlation quadrature, or
+    def __init__(self, backend=None, xc_grid: tuple[int, int] | None = None, eri_engine: str | None = None):
+        """``eri_engine``: where (pq|rs) is computed -- "host" (``nbx_host_eri`` and an upload of the tensor), "device"
+        (``nbx_eri_device``: shells of l <= 2, a backend with ``eri``; raises otherwise) or "auto" (the device where it
+        can serve and the molecule has ``AUTO_ERI_MIN_NAO`` functions or more, the host otherwise); None reads ``NBED_ERI_ENGINE``, default "auto".
+        ``xc_grid``: (radial points per heavy atom, polar angles) of the exchange-correlation quadrature, or
         ("lebedev", level) for the Treutler-Ahlrichs x pruned-Lebedev construction PySCF documents as its default
         (``nbed_amd.xc.build_grid``; None = that construction at its default level 3, which needs SciPy >= 1.15 for
         ``scipy.integrate.lebedev_rule`` -- pass (n_rad, n_theta) for the product grid on an older SciPy).  Matrix elements of
@@ -144,6 +170,10 @@ class BuiltinHFProvider:
         self._be = backend
         self._cache = {}
         self.xc_grid = xc_grid
+        mode = eri_engine if eri_engine is not None else os.environ.get("NBED_ERI_ENGINE", "auto")
+        if mode not in ("auto", "host", "device"):
+            raise NbedDriverError(f"NBED_ERI_ENGINE={mode!r}: expected 'auto', 'host' or 'device'")
+        self.eri_engine = mode
 
     @staticmethod
     def supports(config: NbedConfig) -> bool:
@@ -160,8 +190,49 @@ class BuiltinHFProvider:
 
         key = (config.geometry, str(config.basis).lower(), str(config.unit))
         if key not in self._cache:
-            self._cache[key] = integrals.molecule_integrals(config.geometry, str(config.basis), str(config.unit))
+            if self._eri_route(config) == "host":
+                self._cache[key] = integrals.molecule_integrals(config.geometry, str(config.basis), str(config.unit))
+            else:
+                ints = _DeviceRouteIntegrals(integrals.molecule_integrals(config.geometry, str(config.basis), str(config.unit),
+                                                                          engine="native-1e"))
+                ints.fetch_eri = lambda: self._host_eri(config, ints["basis"])
+                self._cache[key] = ints
         return self._cache[key]
+
+    def _eri_route(self, config: NbedConfig) -> str:
+        """"host" or "device" for this molecule on the provider's backend (``eri_engine``)."""
+        from . import integrals
+
+        if self.eri_engine == "host":
+            return "host"
+        be = self._be
+        if self.eri_engine == "auto" and (not AUTO_ERI_ON_DEVICE or be is None or not hasattr(be, "eri")):
+            return "host"
+        atoms = integrals.parse_geometry(config.geometry, str(config.unit))
+        basis = integrals.Basis(atoms, str(config.basis))
+        lmax = integrals.max_ang(basis)
+        if self.eri_engine == "auto":
+            return "device" if lmax <= 2 and basis.nao >= AUTO_ERI_MIN_NAO else "host"
+        if be is None:
+            be = get_backend()
+        if not hasattr(be, "eri"):
+            raise NbedDriverError(f"eri_engine='device': the {getattr(be, 'name', type(be).__name__)} backend has no "
+                                  "device integral engine")
+        if lmax > 2:
+            raise NbedDriverError(f"eri_engine='device': {config.basis} has shells of l = {lmax}; the device engine covers "
+                                  "l <= 2 (use 'host' or 'auto')")
+        return "device"
+
+    def _host_eri(self, config: NbedConfig, basis):
+        """A host copy of (pq|rs) for a caller that asks the device route's dict for one: read back from the
+        device tensor where one exists, from the host engine otherwise.  Not kept."""
+        from . import integrals
+
+        tail = (config.geometry, str(config.basis).lower(), str(config.unit))
+        for key, slot in self._cache.items():
+            if isinstance(key, tuple) and key[:1] == ("eri_device",) and key[2:] == tail:
+                return np.asarray(slot["be"].to_host(slot["eri"]))
+        return integrals.two_electron_native(basis)
 
     def _eri_kwargs(self, config: NbedConfig, backend) -> dict:
         """``eri=`` / ``eri_packed=`` of the SCF objects of one molecule: the tensor goes to the device
@@ -173,7 +244,15 @@ class BuiltinHFProvider:
         be = backend if backend is not None else (self._be if self._be is not None else get_backend())
         key = ("eri_device", id(be), config.geometry, str(config.basis).lower(), str(config.unit))
         if key not in self._cache:
-            self._cache[key] = {"eri": be.asarray(self._integrals(config)["eri"]), "donor": None}
+            ints = self._integrals(config)
+            if "eri" in ints or not hasattr(be, "eri"):  # the host route, or a cache entry that holds a host tensor
+                if self.eri_engine == "device" and "eri" not in ints:
+                    raise NbedDriverError(f"eri_engine='device': the {getattr(be, 'name', type(be).__name__)} backend has no "
+                                          "device integral engine")
+                eri = be.asarray(ints["eri"])
+            else:  # the device route: no host tensor exists
+                eri = be.eri(ints["basis"])
+            self._cache[key] = {"eri": eri, "donor": None, "be": be}
         slot = self._cache[key]
         out = {"eri": slot["eri"], "backend": be}
         if slot["donor"] is not None:

@@ -531,16 +531,33 @@ def two_electron_native(basis: Basis, nthreads: int = 0, cutoff: float = 1e-16) 
     return out
 
 
+def max_ang(basis: Basis) -> int:
+    """Highest angular momentum of a shell of the basis (the device engine covers l <= 2)."""
+    return max(int(s.ang) for s in basis.shells)
+
+
+def two_electron_device(basis: Basis, backend, cutoff: float = 1e-16):
+    """(pq|rs) as a DEVICE tensor (nao,)*4 from libnbx's device engine (``nbx_eri_device``, csrc/eri.hip): the scheme,
+    pair data and screening of ``two_electron_native`` without the host tensor and its upload.  Shells of l <= 2."""
+    return backend.eri(basis, cutoff=cutoff)
+
+
 def molecule_integrals(xyz: str, basis: str = "sto-3g", unit: str = "angstrom", cart: bool = False,
                        engine: str = "native") -> dict:
     """Everything the embedding driver needs of a molecule: S, hcore = T + V, (pq|rs), e_nuc, the
-    per-atom AO slices and the electron count of the neutral molecule."""
+    per-atom AO slices and the electron count of the neutral molecule.  ``engine="native-1e"``: the host engine's
+    one-electron matrices and no ``"eri"``, with the ``Basis`` under ``"basis"`` for a caller that asks the device
+    for the tensor (``two_electron_device``)."""
     atoms = parse_geometry(xyz, unit)
     bs = Basis(atoms, basis, cart)  # cart: six Cartesian d functions (PySCF's mol.cart), default five spherical
-    s_mat, t_mat, v_mat = one_electron_native(bs) if engine == "native" else one_electron(bs)
-    return {
+    s_mat, t_mat, v_mat = one_electron_native(bs) if engine in ("native", "native-1e") else one_electron(bs)
+    out = {
         "S": s_mat, "T": t_mat, "V": v_mat, "hcore": t_mat + v_mat,
-        "eri": two_electron_native(bs) if engine == "native" else two_electron(bs),
         "e_nuc": nuclear_repulsion(atoms), "ao_slices": bs.ao_slices, "nao": bs.nao,
         "nelectron": sum(NUCLEAR_CHARGE[s] for s, _ in atoms),
     }
+    if engine == "native-1e":
+        out["basis"] = bs
+    else:
+        out["eri"] = two_electron_native(bs) if engine == "native" else two_electron(bs)
+    return out
