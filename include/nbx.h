@@ -807,6 +807,41 @@ int nbx_eri_plan(int nshell, const int* ang, const int* nprim, const int* nfunc,
                  const double* exps, const double* coefs, const double* sph, double cutoff, int64_t* counts_out,
                  int* lds_bytes_out, int* block_out, int64_t* grid_out);
 
+/* ------------------------------------------------------------------ (pq|rs) of a real molecule without the tensor
+ * The same integrals -- gto.Mole.intor("int2e") behind scf.UKS(mol).kernel() at nbed/driver.py:155-191 -- asked for by
+ * the diagonal and by columns, and their pivoted incomplete Cholesky factor (pq|rs) ~ sum_L B_L[pq] B_L[rs], the input
+ * of nbx_jk_df (get_veff at nbed/scf/huzinaga_scf.py:156), DESIGN.md section 13.  The N^4 tensor is never formed.  Shell
+ * arguments, cutoff and screening as nbx_eri_device (the same class kernel with another last stage), and the same
+ * refusals: NBX_E_INVALID for l > 2 and wherever nbx_host_eri refuses the shells.  No atomics, one writer per address:
+ * two calls give the same bits, and a value is the same double wherever it is stored.
+ *
+ * nbx_eri_diagonal: d_diag[p][q] = d_diag[q][p] = (pq|pq), (nao, nao), zeroed and filled on the context's stream.    */
+int nbx_eri_diagonal(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                     const double* exps, const double* coefs, const double* sph, double cutoff, double* d_diag);
+/* nbx_eri_columns (the intor("int2e") of nbed/driver.py:155-191, a column at a time): the shell pairs (ia[k] >= ib[k]),
+ * k < npair, select the columns m = the function pairs (r >= s) of pair 0, then of pair 1, ..., (r, s) row-major
+ * within a pair; d_cols[m][p][q] = d_cols[m][q][p] = (pq|rs), (ncols, nao, nao), zeroed and filled on the context's
+ * stream (quartets the Schwarz test drops stay zero).  The values are those of nbx_eri_device, bit for bit, and do not
+ * depend on which other pairs are listed.                                                                       */
+int nbx_eri_columns(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                    const double* exps, const double* coefs, const double* sph, double cutoff, int npair, const int* ia,
+                    const int* ib, double* d_cols);
+/* nbx_eri_cholesky (intor("int2e") at nbed/driver.py:155-191 in the factorised form get_veff at
+ * nbed/scf/huzinaga_scf.py:156 can contract): shell-blocked pivoted Cholesky, host driven with one small read-back per step.
+ *   tol         stop when the largest residual diagonal is <= tol; then |(pq|rs) - sum_L B_L[pq] B_L[rs]| <= tol for
+ *               every element (the residual is positive semi-definite).  Finite and >= 1e-12, else NBX_E_INVALID.
+ *   max_rank    >= 1 (else NBX_E_INVALID): room of d_b in slices.  Reaching it first is not an error: *resid_out > tol.
+ *   d_b         (max_rank, nao, nao) DEVICE: slices [0, *rank_out) are written, each symmetric bit for bit (the input
+ *               format of nbx_jk_df); the others, and all of it when the call is refused, are left untouched.
+ *   rank_out, resid_out   HOST: vectors written; largest remaining residual diagonal.
+ * The call returns with the stream idle.                                                                        */
+int nbx_eri_cholesky(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                     const double* exps, const double* coefs, const double* sph, double cutoff, double tol,
+                     int64_t max_rank, double* d_b, int64_t* rank_out, double* resid_out);
+/* Host bookkeeping of the last nbx_eri_cholesky call on this thread (the intor("int2e") call of
+ * nbed/driver.py:155-191 has no counterpart of it): steps taken and columns (pq|m) computed.                 */
+int nbx_eri_cholesky_steps(int64_t* steps, int64_t* columns);
+
 /* ------------------------------------------------------------------ coupled cluster (csrc/ccsd.hip)
  * What surrounds the GEMMs of a spin-orbital CCSD (nbed_amd/ccsd_gpu.py): the reference runs PySCF's
  * cc.CCSD on the embedded object (nbed/driver.py:1105-1135); here the amplitude equations of

@@ -191,6 +191,11 @@ SIGNATURES = {
     "nbx_eri_class_ms": (c_int, [_P, POINTER(c_double)]),
     "nbx_eri_plan": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_double, POINTER(c_int64), POINTER(c_int), POINTER(c_int),
                              POINTER(c_int64)]),
+    "nbx_eri_diagonal": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_double, _P]),
+    "nbx_eri_columns": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_double, c_int, _P, _P, _P]),
+    "nbx_eri_cholesky": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_int64, _P, POINTER(c_int64),
+                                 POINTER(c_double)]),
+    "nbx_eri_cholesky_steps": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
     "nbx_huz_cycle": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                               c_int, _P, _P]),
     "nbx_huz_cycle_jk": (c_int, [_P, POINTER(HuzState), _P]),

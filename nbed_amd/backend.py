@@ -529,6 +529,62 @@ class HipBackend:
         self._call("nbx_eri_device", len(basis.shells), *(ptr(a) for a in arrays), float(cutoff), self._p(out))
         return out
 
+    def _eri_shell_args(self, basis, what: str):
+        from .integrals import _shell_arrays, max_ang
+
+        if max_ang(basis) > 2:
+            raise _nbx.NbxError(_nbx.NBX_E_INVALID, f"{what}: the device integral engine covers shells of l <= 2 (s, p, d); "
+                                "f shells are the host engine's (integrals.two_electron_native)")
+        arrays = _shell_arrays(basis)  # (kept alive by the caller until the library call has returned)
+        return arrays, [a.ctypes.data_as(ctypes.c_void_p) for a in arrays]
+
+    def eri_diagonal(self, basis, cutoff: float = 1e-16):
+        """d[p, q] = (pq|pq) of ``basis`` as a device tensor (nao, nao), exactly symmetric (nbx_eri_diagonal): the
+        integral engine's class kernel on the quartets (ij, ij) only."""
+        arrays, ptrs = self._eri_shell_args(basis, "eri_diagonal")
+        out = self.empty((basis.nao, basis.nao))
+        self._call("nbx_eri_diagonal", len(basis.shells), *ptrs, float(cutoff), self._p(out))
+        return out
+
+    def eri_columns(self, basis, shell_pairs, cutoff: float = 1e-16):
+        """(ncols, nao, nao): the columns (pq|rs) of the function pairs (r >= s) of the listed shell pairs (ia >= ib), in
+        the order listed and (r, s) row-major within a pair; each slice exactly symmetric (nbx_eri_columns)."""
+        arrays, ptrs = self._eri_shell_args(basis, "eri_columns")
+        pairs = [(int(a), int(b)) for a, b in shell_pairs]
+        nf = [int(sh.sph.shape[0]) for sh in basis.shells]
+        if any(not 0 <= b <= a < len(nf) for a, b in pairs):
+            raise ValueError(f"eri_columns: shell pairs must be (ia, ib) with {len(nf)} > ia >= ib >= 0")
+        ncols = sum(nf[a] * (nf[a] + 1) // 2 if a == b else nf[a] * nf[b] for a, b in pairs)
+        ia = np.array([a for a, _ in pairs], dtype=np.int32)
+        ib = np.array([b for _, b in pairs], dtype=np.int32)
+        out = self.empty((ncols, basis.nao, basis.nao))
+        self._call("nbx_eri_columns", len(basis.shells), *ptrs, float(cutoff), len(pairs), ia.ctypes.data_as(ctypes.c_void_p),
+                   ib.ctypes.data_as(ctypes.c_void_p), self._p(out))
+        return out
+
+    def eri_cholesky(self, basis, tol: float = 1e-8, max_rank: int | None = None, cutoff: float = 1e-16):
+        """The factor B (rank, nao, nao) of (pq|rs) ~ sum_L B[L, p, q] B[L, r, s] from a pivoted incomplete Cholesky
+        decomposition on the device (nbx_eri_cholesky): every element of the tensor is reproduced within ``tol``, the
+        tensor itself is never formed, and B is ``jk_df`` / ``jk_factor``'s input.  A view of an allocation of
+        ``max_rank`` slices (default min(N (N + 1) / 2, 16 N)); ValueError if ``max_rank`` vectors do not reach ``tol``.
+        ``eri_cholesky_info`` keeps rank, residual, steps and columns of the last call."""
+        arrays, ptrs = self._eri_shell_args(basis, "eri_cholesky")
+        n = int(basis.nao)
+        if max_rank is None:
+            max_rank = min(n * (n + 1) // 2, 16 * n)
+        buf = self.empty((max(int(max_rank), 1), n, n))
+        rank, resid = ctypes.c_int64(0), c_double(0.0)
+        self._call("nbx_eri_cholesky", len(basis.shells), *ptrs, float(cutoff), float(tol), int(max_rank), self._p(buf),
+                   ctypes.byref(rank), ctypes.byref(resid))
+        steps, columns = ctypes.c_int64(0), ctypes.c_int64(0)
+        _nbx.check(self.lib, self.lib.nbx_eri_cholesky_steps(ctypes.byref(steps), ctypes.byref(columns)))
+        self.eri_cholesky_info = {"rank": int(rank.value), "resid": float(resid.value), "steps": int(steps.value),
+                                  "columns": int(columns.value)}
+        if resid.value > tol:
+            raise ValueError(f"eri_cholesky: tol = {tol:g} was not reached: the largest residual diagonal is "
+                             f"{resid.value:.3e} after max_rank = {int(max_rank)} vectors")
+        return buf[: int(rank.value)]
+
     def eri_class_ms(self) -> np.ndarray:
         """Milliseconds of each class launch (5, 5) of the last ``eri`` call made under ``profile(slots=[PROF_ERI])``."""
         ms = (c_double * _nbx.ERI_CLASSES)()
@@ -912,6 +968,40 @@ class HipBackend:
         work = self._workspace("jk_df", nbytes)
         self._call("nbx_jk_df", n, int(b.shape[0]), self._p(b), ndm, self._p(c3), (ctypes.c_int64 * ndm)(*occ), self._p(out),
                    self._p(work), nbytes)
+        return out
+
+    # doubles of the intermediate D_x B_L a jk_factor call holds at a time (256 MB)
+    JK_FACTOR_CHUNK_DOUBLES = 1 << 25
+
+    def jk_factor(self, b, dm):
+        """J and K of a DENSITY from the factor ``b`` (naux, N, N), every slice symmetric: J = sum_L B_L <B_L, D_tot>,
+        K_x = sum_L B_L D_x B_L.  ``dm`` is (N, N) or (ndm, N, N); returns (1 + ndm, N, N) as ``jk`` and ``jk_packed`` do.
+        All of it is nbx_gemm: two matrix-vector products for J; per density the batched products D_x B_L and one
+        product over the index (L, q), K_x = sum_(L,q) B_L[q, :]^T (D_x B_L)[q, :].  ``jk_df`` is the cheaper form for
+        a caller that has the occupied orbitals."""
+        dm3 = (dm if dm.dim() == 3 else dm.unsqueeze(0)).contiguous()  # (the products below address both by ld = N)
+        b = b.contiguous()
+        ndm, n = int(dm3.shape[0]), int(dm3.shape[-1])
+        naux = int(b.shape[0])
+        if tuple(b.shape[1:]) != (n, n):
+            raise ValueError(f"jk_factor: factor of shape {tuple(b.shape)} for densities of {n} functions")
+        out = self.empty((1 + ndm, n, n))
+        if naux == 0:
+            out.zero_()
+            return out
+        dtot = self.copy(dm3[0])
+        for x in range(1, ndm):
+            self.axpby(1.0, dm3[x], 1.0, dtot)
+        v = self.empty((naux,))
+        self.gemm_raw("N", "N", naux, 1, n * n, 1.0, b, n * n, 0, dtot, 1, 0, 0.0, v, 1, 0, 1)
+        self.gemm_raw("N", "N", 1, n * n, naux, 1.0, v, naux, 0, b, n * n, 0, 0.0, out[0], n * n, 0, 1)
+        chunk = max(1, min(naux, self.JK_FACTOR_CHUNK_DOUBLES // (n * n)))
+        tmp = self._workspace("jk_factor", 8 * chunk * n * n)
+        for x in range(ndm):
+            for l0 in range(0, naux, chunk):
+                nl = min(chunk, naux - l0)
+                self.gemm_raw("N", "N", n, n, n, 1.0, dm3[x], n, 0, b[l0:], n, n * n, 0.0, tmp, n, n * n, nl)
+                self.gemm_raw("T", "N", n, n, nl * n, 1.0, b[l0:], n, 0, tmp, n, 0, 0.0 if l0 == 0 else 1.0, out[1 + x], n, 0, 1)
         return out
 
     def async_to_host(self, d_vals):

@@ -13,8 +13,11 @@
 //           eight images.  No atomics: a quartet's sums run in the host engine's order, so two runs are
 //           bit-identical, and where shells coincide the lane that stores is the one whose value the host engine's
 //           last write leaves, so the images are the same double.
-#include "ints_md.h"
-#include "nbx_common.h"
+//
+// The last stage is one of three sinks chosen at compile time: the dense tensor above; the
+// diagonal d[p][q] = (pq|pq) from the quartets (ij, ij); and the columns (pq|rs) of selected shell pairs, which
+// csrc/eri_cd.hip decomposes.  All three store by the same rule, so an integral is the same double in each.
+#include "eri_device.h"
 
 #include <algorithm>
 #include <mutex>
@@ -22,6 +25,7 @@
 namespace {
 
 using namespace nbx_md;
+using namespace nbx_eri;
 
 constexpr int DEV_LMAX = 2;              // per shell on the device (f shells stay on the host engine)
 constexpr int NLP = 2 * DEV_LMAX + 1;    // pair orders l_ab = 0 .. 4
@@ -32,9 +36,6 @@ constexpr int ERI_BLOCK = 64;            // one wavefront per workgroup: the wor
 constexpr int ERI_CUS = 256;             // MI355X
 constexpr int ERI_LDS_PER_CU = 160 * 1024;
 constexpr int ERI_MAX_WG_PER_CU = 16;
-
-struct DevShell { int l, ncart, nsph, ao0; long long sph_off; };
-struct DevPair { int ia, ib, nab, nprim; long long prim_off, h_off; };
 
 __host__ __device__ constexpr int nherm_c(int l) { return (l + 1) * (l + 2) * (l + 3) / 6; }
 // most Cartesian component pairs of a shell pair of order lab with l <= 2 per shell: ss, ps, pp|ds, dp, dd
@@ -62,19 +63,6 @@ inline int lds_bytes_of(int lab, int lcd) { return int(LDS_BYTES[lab * NLP + lcd
 inline int wg_per_cu(int lab, int lcd) { return std::min(ERI_MAX_WG_PER_CU, ERI_LDS_PER_CU / lds_bytes_of(lab, lcd)); }
 inline int64_t grid_of(int lab, int lcd, int64_t count) { return std::min<int64_t>(count, int64_t(ERI_CUS) * wg_per_cu(lab, lcd)); }
 
-struct EriArgs {
-    const DevShell* shells;
-    const DevPair* pairs;
-    const double* prim;   // (p, Px, Py, Pz) per surviving primitive pair
-    const double* h;      // Hermite densities [prim][nab][nh]
-    const double* sph;
-    const double* boys;   // BoysTable::f
-    const int* tabs;      // NLP x NH_MAX packed (t, u, v) in HermIndex order, then NR_MAX sorted by t + u + v
-    double* out;
-    double pref0;         // 2 pi^(5/2)
-    int nao;
-};
-
 // BoysTable::eval
 template <int L>
 __device__ __forceinline__ void boys_eval(const double* __restrict__ tab, double t, double* out) {
@@ -100,8 +88,21 @@ __device__ __forceinline__ void boys_eval(const double* __restrict__ tab, double
     for (int m = L; m > 0; --m) out[m - 1] = (2.0 * t * out[m] + et) / (2 * m - 1);
 }
 
-template <int LAB, int LCD>
-__global__ __launch_bounds__(ERI_BLOCK) void eri_class_kernel(EriArgs a, const uint2* __restrict__ quartets, long long nq) {
+// The sinks of eri_class_kernel: where the spherical block of a quartet goes.
+constexpr int SINK_DENSE = 0;   // eight images into the (nao)^4 tensor
+constexpr int SINK_DIAG = 1;    // quartets (ij, ij): d[p][q] = d[q][p] = (pq|pq)
+constexpr int SINK_COLUMN = 2;  // col[m][p][q] = col[m][q][p] = (pq|m), m a function pair (r >= s) of a selected shell pair
+
+// column of the function pair (x, y) of a selected shell pair whose first column is m0: (r, s) row-major, r >= s
+__device__ __forceinline__ size_t column_of(unsigned m0, bool same, int x, int y, int ny) {
+    if (!same) return size_t(m0) + x * ny + y;
+    const int hi = x > y ? x : y, lo = x > y ? y : x;
+    return size_t(m0) + hi * (hi + 1) / 2 + lo;
+}
+
+template <int LAB, int LCD, int SINK>
+__global__ __launch_bounds__(ERI_BLOCK) void eri_class_kernel(EriArgs a, const uint2* __restrict__ quartets,
+                                                              const uint2* __restrict__ aux, long long nq) {
     constexpr int L = LAB + LCD, E = cube_edge(LAB, LCD), CUBE = cube_doubles(LAB, LCD);
     constexpr int NHAB = nherm_c(LAB), NHCD = nherm_c(LCD), NR = nherm_c(L);
     constexpr int BLK = blk_doubles(LAB, LCD), MAXR = (BLK + ERI_BLOCK - 1) / ERI_BLOCK;
@@ -240,12 +241,14 @@ __global__ __launch_bounds__(ERI_BLOCK) void eri_class_kernel(EriArgs a, const u
             double* s = src; src = dst; dst = s;
         }
 
-        // Eight images.  Where shells coincide (ia == ib, ic == id, ij == kl) several (a, b, c, d) of this block name
-        // the same integral; the host engine's loops leave the value of the last of them in (a, b, c, d) order in all
-        // their images, so only that one is stored here.
+        // Where shells coincide (ia == ib, ic == id, ij == kl) several (a, b, c, d) of this block name the same integral;
+        // the host engine's loops leave the value of the last of them in (a, b, c, d) order in all their images, so only
+        // that one is stored, by every sink: to the eight images of the tensor, or to those of them the sink keeps.
         const int na = dims[0], nb = dims[1], nc = dims[2], nd = dims[3];
         const bool same_ab = ab.ia == ab.ib, same_cd = cd.ia == cd.ib, same_q = ql.x == ql.y;
         const size_t n = size_t(a.nao), n2 = n * n, n3 = n2 * n;
+        uint2 col = make_uint2(0u, 0u);
+        if constexpr (SINK == SINK_COLUMN) col = aux[qi];
         for (int idx = lane; idx < na * nb * nc * nd; idx += ERI_BLOCK) {
             int t = idx;
             const int d = t % nd; t /= nd;
@@ -265,29 +268,56 @@ __global__ __launch_bounds__(ERI_BLOCK) void eri_class_kernel(EriArgs a, const u
             const double val = src[idx];
             const size_t p = sh[0].ao0 + aa, q = sh[1].ao0 + b, r = sh[2].ao0 + c, s = sh[3].ao0 + d;
             double* out = a.out;
-            out[p * n3 + q * n2 + r * n + s] = val;
-            out[q * n3 + p * n2 + r * n + s] = val;
-            out[p * n3 + q * n2 + s * n + r] = val;
-            out[q * n3 + p * n2 + s * n + r] = val;
-            out[r * n3 + s * n2 + p * n + q] = val;
-            out[s * n3 + r * n2 + p * n + q] = val;
-            out[r * n3 + s * n2 + q * n + p] = val;
-            out[s * n3 + r * n2 + q * n + p] = val;
+            if constexpr (SINK == SINK_DENSE) {
+                out[p * n3 + q * n2 + r * n + s] = val;
+                out[q * n3 + p * n2 + r * n + s] = val;
+                out[p * n3 + q * n2 + s * n + r] = val;
+                out[q * n3 + p * n2 + s * n + r] = val;
+                out[r * n3 + s * n2 + p * n + q] = val;
+                out[s * n3 + r * n2 + p * n + q] = val;
+                out[r * n3 + s * n2 + q * n + p] = val;
+                out[s * n3 + r * n2 + q * n + p] = val;
+            } else if constexpr (SINK == SINK_DIAG) {
+                // (ij, ij): the block's element (a, b, a, b) names (pq|pq).  Within one shell (b, a, a, b) names it too,
+                // but the last of the orbit in (a, b, c, d) order is (hi, lo, hi, lo), which has this form itself.
+                if (aa == c && b == d) {
+                    out[p * n + q] = val;
+                    out[q * n + p] = val;
+                }
+            } else {
+                // the selected pair is the ket (col.y == 0), the bra (1), or both (ij == kl)
+                if (col.y == 0u) {
+                    double* slice = out + column_of(col.x, same_cd, c, d, nd) * n2;
+                    slice[p * n + q] = val;
+                    slice[q * n + p] = val;
+                }
+                if (col.y != 0u || same_q) {
+                    double* slice = out + column_of(col.x, same_ab, aa, b, nb) * n2;
+                    slice[r * n + s] = val;
+                    slice[s * n + r] = val;
+                }
+            }
         }
         __syncthreads();  // the next quartet reuses the buffers
     }
 }
 
-template <int LAB, int LCD>
-void launch_class(hipStream_t stream, const EriArgs& args, const uint2* d_quartets, int64_t count) {
-    hipLaunchKernelGGL((eri_class_kernel<LAB, LCD>), dim3((unsigned)grid_of(LAB, LCD, count)), dim3(ERI_BLOCK), 0, stream, args,
-                       d_quartets, (long long)count);
+template <int LAB, int LCD, int SINK>
+void launch_class(hipStream_t stream, const EriArgs& args, const uint2* d_quartets, const uint2* d_aux, int64_t count) {
+    hipLaunchKernelGGL((eri_class_kernel<LAB, LCD, SINK>), dim3((unsigned)grid_of(LAB, LCD, count)), dim3(ERI_BLOCK), 0, stream, args,
+                       d_quartets, d_aux, (long long)count);
 }
 
-using launch_fn = void (*)(hipStream_t, const EriArgs&, const uint2*, int64_t);
-#define ERI_ROW(A) launch_class<A, 0>, launch_class<A, 1>, launch_class<A, 2>, launch_class<A, 3>, launch_class<A, 4>
-const launch_fn LAUNCH[NCLASS] = {ERI_ROW(0), ERI_ROW(1), ERI_ROW(2), ERI_ROW(3), ERI_ROW(4)};
+using launch_fn = void (*)(hipStream_t, const EriArgs&, const uint2*, const uint2*, int64_t);
+#define ERI_ROW(A, S) launch_class<A, 0, S>, launch_class<A, 1, S>, launch_class<A, 2, S>, launch_class<A, 3, S>, launch_class<A, 4, S>
+const launch_fn LAUNCH[NCLASS] = {ERI_ROW(0, SINK_DENSE), ERI_ROW(1, SINK_DENSE), ERI_ROW(2, SINK_DENSE), ERI_ROW(3, SINK_DENSE),
+                                  ERI_ROW(4, SINK_DENSE)};
+const launch_fn LAUNCH_COLUMN[NCLASS] = {ERI_ROW(0, SINK_COLUMN), ERI_ROW(1, SINK_COLUMN), ERI_ROW(2, SINK_COLUMN),
+                                         ERI_ROW(3, SINK_COLUMN), ERI_ROW(4, SINK_COLUMN)};
 #undef ERI_ROW
+// a diagonal quartet is (ij, ij): only the classes l_ab == l_cd exist
+const launch_fn LAUNCH_DIAG[NLP] = {launch_class<0, 0, SINK_DIAG>, launch_class<1, 1, SINK_DIAG>, launch_class<2, 2, SINK_DIAG>,
+                                    launch_class<3, 3, SINK_DIAG>, launch_class<4, 4, SINK_DIAG>};
 
 // ------------------------------------------------------------------------------------------ host side
 struct Plan {
@@ -296,15 +326,22 @@ struct Plan {
     std::vector<uint2> quartets;  // class after class (want_lists)
 };
 
-// What both entry points start from; NBX_E_INVALID where nbx_host_eri refuses the shells, and for l > 2.
-int make_plan(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres, const double* exps,
-              const double* coefs, const double* sph, double cutoff, bool want_lists, Plan& pl) {
+// Shells, index tables and pair data; NBX_E_INVALID where nbx_host_eri refuses the shells, and for l > 2.
+int make_engine(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres, const double* exps,
+                const double* coefs, const double* sph, double cutoff, Engine& eng) {
     if (nshell <= 0 || !ang || !nprim || !nfunc || !centres || !exps || !coefs || !sph) return NBX_E_INVALID;
-    Engine& eng = pl.eng;
     eng.cutoff = cutoff;
     if (engine_shells(eng, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, DEV_LMAX) != NBX_OK) return NBX_E_INVALID;
     engine_tables(eng);
     engine_pairs(eng, std::min(pool_size(0), 16));
+    return NBX_OK;
+}
+
+// What nbx_eri_plan and nbx_eri_device start from: the engine and the canonical quartets of the dense tensor.
+int make_plan(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres, const double* exps,
+              const double* coefs, const double* sph, double cutoff, bool want_lists, Plan& pl) {
+    Engine& eng = pl.eng;
+    if (make_engine(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, eng) != NBX_OK) return NBX_E_INVALID;
     const int64_t npair = int64_t(eng.pairs.size());
     auto each = [&](auto&& fn) {
         for (int64_t ij = npair - 1; ij >= 0; --ij) {
@@ -327,6 +364,78 @@ int make_plan(int nshell, const int* ang, const int* nprim, const int* nfunc, co
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// One host image of everything but the lists: shells, pairs, primitives, H, sph, Boys table, index tables.
+struct Image {
+    std::vector<char> bytes;
+    size_t o_shell, o_pair, o_prim, o_h, o_sph, o_boys, o_tabs;
+};
+
+void build_image(const Engine& eng, Image& im) {
+    const size_t nshells = eng.shells.size(), npairs = eng.pairs.size();
+    size_t nprims = 0, nh = 0, nsph = 0;
+    for (const Pair& pr : eng.pairs) { nprims += size_t(pr.nprim); nh += pr.h.size(); }
+    for (const Shell& s : eng.shells) nsph += size_t(s.nsph) * s.ncart_;
+    im.o_shell = 0;
+    im.o_pair = align256(im.o_shell + nshells * sizeof(DevShell));
+    im.o_prim = align256(im.o_pair + npairs * sizeof(DevPair));
+    im.o_h = align256(im.o_prim + nprims * 4 * sizeof(double));
+    im.o_sph = align256(im.o_h + nh * sizeof(double));
+    im.o_boys = align256(im.o_sph + nsph * sizeof(double));
+    im.o_tabs = align256(im.o_boys + eng.boys.f.size() * sizeof(double));
+    im.bytes.assign(align256(im.o_tabs + (NLP * NH_MAX + NR_MAX) * sizeof(int)), 0);
+    std::vector<char>& img = im.bytes;
+    DevShell* ds = reinterpret_cast<DevShell*>(&img[im.o_shell]);
+    size_t so = 0;
+    double* dsph = reinterpret_cast<double*>(&img[im.o_sph]);
+    for (size_t s = 0; s < nshells; ++s) {
+        const Shell& sh = eng.shells[s];
+        ds[s] = {sh.l, sh.ncart_, sh.nsph, sh.ao0, (long long)so};
+        std::memcpy(dsph + so, sh.sph, sizeof(double) * sh.nsph * sh.ncart_);
+        so += size_t(sh.nsph) * sh.ncart_;
+    }
+    DevPair* dp = reinterpret_cast<DevPair*>(&img[im.o_pair]);
+    double* dprim = reinterpret_cast<double*>(&img[im.o_prim]);
+    double* dh = reinterpret_cast<double*>(&img[im.o_h]);
+    size_t po = 0, ho = 0;
+    for (size_t k = 0; k < npairs; ++k) {
+        const Pair& pr = eng.pairs[k];
+        dp[k] = {pr.ia, pr.ib, pr.nab, pr.nprim, (long long)po, (long long)ho};
+        for (int i = 0; i < pr.nprim; ++i) {
+            double* q = dprim + 4 * (po + i);
+            q[0] = pr.p[i]; q[1] = pr.px[i]; q[2] = pr.py[i]; q[3] = pr.pz[i];
+        }
+        if (!pr.h.empty()) std::memcpy(dh + ho, pr.h.data(), sizeof(double) * pr.h.size());
+        po += size_t(pr.nprim);
+        ho += pr.h.size();
+    }
+    std::memcpy(&img[im.o_boys], eng.boys.f.data(), sizeof(double) * eng.boys.f.size());
+    int* tabs = reinterpret_cast<int*>(&img[im.o_tabs]);
+    for (int l = 0; l < NLP; ++l)
+        for (int k = 0; k < eng.hidx[l].n; ++k)
+            tabs[l * NH_MAX + k] = eng.hidx[l].tuv[k][0] | (eng.hidx[l].tuv[k][1] << 8) | (eng.hidx[l].tuv[k][2] << 16);
+    int k = 0;  // every (t, u, v) of order <= 8 by total order: the entries of a recursion pass are a prefix
+    const HermIndex top(2 * NLP - 2);
+    for (int deg = 0; deg <= 2 * NLP - 2; ++deg)
+        for (int m = 0; m < top.n; ++m)
+            if (top.tuv[m][0] + top.tuv[m][1] + top.tuv[m][2] == deg)
+                tabs[NLP * NH_MAX + k++] = top.tuv[m][0] | (top.tuv[m][1] << 8) | (top.tuv[m][2] << 16);
+}
+
+EriArgs args_of(const char* d_img, const Image& im, const Engine& eng, double* out) {
+    EriArgs args;
+    args.shells = reinterpret_cast<const DevShell*>(d_img + im.o_shell);
+    args.pairs = reinterpret_cast<const DevPair*>(d_img + im.o_pair);
+    args.prim = reinterpret_cast<const double*>(d_img + im.o_prim);
+    args.h = reinterpret_cast<const double*>(d_img + im.o_h);
+    args.sph = reinterpret_cast<const double*>(d_img + im.o_sph);
+    args.boys = reinterpret_cast<const double*>(d_img + im.o_boys);
+    args.tabs = reinterpret_cast<const int*>(d_img + im.o_tabs);
+    args.out = out;
+    args.pref0 = 2.0 * std::pow(M_PI, 2.5);
+    args.nao = eng.nao;
+    return args;
+}
 
 std::mutex g_times_mutex;
 std::vector<hipEvent_t> g_events;  // (start, stop) per class of the last bracketed nbx_eri_device call
@@ -373,55 +482,9 @@ extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const in
     const size_t n = size_t(eng.nao);
     NBX_HIP(hipMemsetAsync(out_device, 0, sizeof(double) * n * n * n * n, ctx->stream));
 
-    // one host image of everything but the lists: shells, pairs, primitives, H, sph, Boys table, index tables
-    const size_t nshells = eng.shells.size(), npairs = eng.pairs.size();
-    size_t nprims = 0, nh = 0, nsph = 0;
-    for (const Pair& pr : eng.pairs) { nprims += size_t(pr.nprim); nh += pr.h.size(); }
-    for (const Shell& s : eng.shells) nsph += size_t(s.nsph) * s.ncart_;
-    const size_t o_shell = 0, o_pair = align256(o_shell + nshells * sizeof(DevShell)),
-                 o_prim = align256(o_pair + npairs * sizeof(DevPair)), o_h = align256(o_prim + nprims * 4 * sizeof(double)),
-                 o_sph = align256(o_h + nh * sizeof(double)), o_boys = align256(o_sph + nsph * sizeof(double)),
-                 o_tabs = align256(o_boys + eng.boys.f.size() * sizeof(double)),
-                 bytes = align256(o_tabs + (NLP * NH_MAX + NR_MAX) * sizeof(int));
-    std::vector<char> img(bytes, 0);
-    {
-        DevShell* ds = reinterpret_cast<DevShell*>(&img[o_shell]);
-        size_t so = 0;
-        double* dsph = reinterpret_cast<double*>(&img[o_sph]);
-        for (size_t s = 0; s < nshells; ++s) {
-            const Shell& sh = eng.shells[s];
-            ds[s] = {sh.l, sh.ncart_, sh.nsph, sh.ao0, (long long)so};
-            std::memcpy(dsph + so, sh.sph, sizeof(double) * sh.nsph * sh.ncart_);
-            so += size_t(sh.nsph) * sh.ncart_;
-        }
-        DevPair* dp = reinterpret_cast<DevPair*>(&img[o_pair]);
-        double* dprim = reinterpret_cast<double*>(&img[o_prim]);
-        double* dh = reinterpret_cast<double*>(&img[o_h]);
-        size_t po = 0, ho = 0;
-        for (size_t k = 0; k < npairs; ++k) {
-            const Pair& pr = eng.pairs[k];
-            dp[k] = {pr.ia, pr.ib, pr.nab, pr.nprim, (long long)po, (long long)ho};
-            for (int i = 0; i < pr.nprim; ++i) {
-                double* q = dprim + 4 * (po + i);
-                q[0] = pr.p[i]; q[1] = pr.px[i]; q[2] = pr.py[i]; q[3] = pr.pz[i];
-            }
-            if (!pr.h.empty()) std::memcpy(dh + ho, pr.h.data(), sizeof(double) * pr.h.size());
-            po += size_t(pr.nprim);
-            ho += pr.h.size();
-        }
-        std::memcpy(&img[o_boys], eng.boys.f.data(), sizeof(double) * eng.boys.f.size());
-        int* tabs = reinterpret_cast<int*>(&img[o_tabs]);
-        for (int l = 0; l < NLP; ++l)
-            for (int k = 0; k < eng.hidx[l].n; ++k)
-                tabs[l * NH_MAX + k] = eng.hidx[l].tuv[k][0] | (eng.hidx[l].tuv[k][1] << 8) | (eng.hidx[l].tuv[k][2] << 16);
-        int k = 0;  // every (t, u, v) of order <= 8 by total order: the entries of a recursion pass are a prefix
-        const HermIndex top(2 * NLP - 2);
-        for (int deg = 0; deg <= 2 * NLP - 2; ++deg)
-            for (int m = 0; m < top.n; ++m)
-                if (top.tuv[m][0] + top.tuv[m][1] + top.tuv[m][2] == deg)
-                    tabs[NLP * NH_MAX + k++] = top.tuv[m][0] | (top.tuv[m][1] << 8) | (top.tuv[m][2] << 16);
-    }
-
+    Image im;
+    build_image(eng, im);
+    const size_t bytes = im.bytes.size();
     char* d_img = nullptr;
     uint2* d_q = nullptr;
     const size_t qbytes = std::max<size_t>(pl.quartets.size() * sizeof(uint2), 8);
@@ -436,7 +499,7 @@ extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const in
         nbx_set_error("nbx_eri_device: %s -> %s", what, hipGetErrorString(e));
         rc = NBX_E_HIP;
     };
-    hipError_t e = hipMemcpyAsync(d_img, img.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(d_img, im.bytes.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) fail(e, "upload of the pair data");
     if (rc == NBX_OK && !pl.quartets.empty()) {
         e = hipMemcpyAsync(d_q, pl.quartets.data(), pl.quartets.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
@@ -448,17 +511,7 @@ extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const in
         if (e != hipSuccess) fail(e, "hipStreamSynchronize");
     }
     if (rc == NBX_OK) {
-        EriArgs args;
-        args.shells = reinterpret_cast<const DevShell*>(d_img + o_shell);
-        args.pairs = reinterpret_cast<const DevPair*>(d_img + o_pair);
-        args.prim = reinterpret_cast<const double*>(d_img + o_prim);
-        args.h = reinterpret_cast<const double*>(d_img + o_h);
-        args.sph = reinterpret_cast<const double*>(d_img + o_sph);
-        args.boys = reinterpret_cast<const double*>(d_img + o_boys);
-        args.tabs = reinterpret_cast<const int*>(d_img + o_tabs);
-        args.out = out_device;
-        args.pref0 = 2.0 * std::pow(M_PI, 2.5);
-        args.nao = eng.nao;
+        const EriArgs args = args_of(d_img, im, eng, out_device);
         const bool timed = ctx->profiling && ((ctx->prof_mask >> NBX_PROF_ERI) & 1u);
         std::lock_guard<std::mutex> lock(g_times_mutex);
         if (timed) drop_events();
@@ -469,7 +522,7 @@ extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const in
             hipEvent_t ev[2] = {nullptr, nullptr};
             if (timed && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess)
                 (void)hipEventRecord(ev[0], ctx->stream);
-            LAUNCH[c](ctx->stream, args, d_q + off, cnt);
+            LAUNCH[c](ctx->stream, args, d_q + off, nullptr, cnt);
             e = hipGetLastError();
             if (e != hipSuccess) fail(e, "launch");
             if (timed && ev[0] && ev[1]) {
@@ -483,6 +536,137 @@ extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const in
     }
     (void)hipFreeAsync(d_q, ctx->stream);
     (void)hipFreeAsync(d_img, ctx->stream);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------ diagonal and columns
+namespace nbx_eri {
+
+int session_open(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                 const double* exps, const double* coefs, const double* sph, double cutoff, Session& s) {
+    if (make_engine(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, s.eng) != NBX_OK) return NBX_E_INVALID;
+    s.stream = ctx->stream;
+    s.cutoff = cutoff;
+    Image im;
+    build_image(s.eng, im);
+    NBX_HIP(hipMallocAsync(reinterpret_cast<void**>(&s.d_img), im.bytes.size(), s.stream));
+    hipError_t e = hipMemcpyAsync(s.d_img, im.bytes.data(), im.bytes.size(), hipMemcpyHostToDevice, s.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s.stream);  // the image dies with this call
+    if (e != hipSuccess) {
+        nbx_set_error("upload of the pair data -> %s", hipGetErrorString(e));
+        session_close(s);
+        return NBX_E_HIP;
+    }
+    s.args = args_of(s.d_img, im, s.eng, nullptr);
+    return NBX_OK;
+}
+
+void session_close(Session& s) {
+    if (s.d_img) (void)hipFreeAsync(s.d_img, s.stream);
+    s.d_img = nullptr;
+}
+
+// memset, the lists behind it (stream-ordered scratch), one launch per non-empty class
+static int run_lists(Session& s, const launch_fn* table, bool diag, const int64_t* counts, const uint2* quartets,
+                     const uint2* aux, size_t total, double* out, size_t out_doubles, const int* col_pq, size_t ncols,
+                     int* d_col_pq) {
+    NBX_HIP(hipMemsetAsync(out, 0, sizeof(double) * out_doubles, s.stream));
+    if (d_col_pq && ncols) NBX_HIP(hipMemcpyAsync(d_col_pq, col_pq, sizeof(int) * ncols, hipMemcpyHostToDevice, s.stream));
+    if (total == 0) return NBX_OK;
+    uint2* d_q = nullptr;
+    const size_t half = align256(total * sizeof(uint2));
+    if (hipMallocAsync(reinterpret_cast<void**>(&d_q), 2 * half, s.stream) != hipSuccess) {
+        nbx_set_error("%zu bytes of quartet lists do not fit", 2 * half);
+        return NBX_E_NOMEM;
+    }
+    uint2* d_aux = aux ? reinterpret_cast<uint2*>(reinterpret_cast<char*>(d_q) + half) : nullptr;
+    int rc = NBX_OK;
+    hipError_t e = hipMemcpyAsync(d_q, quartets, total * sizeof(uint2), hipMemcpyHostToDevice, s.stream);
+    if (e == hipSuccess && aux) e = hipMemcpyAsync(d_aux, aux, total * sizeof(uint2), hipMemcpyHostToDevice, s.stream);
+    EriArgs args = s.args;
+    args.out = out;
+    int64_t off = 0;
+    for (int c = 0; c < NCLASS && e == hipSuccess; ++c) {
+        if (counts[c] == 0) continue;
+        (diag ? table[c / NLP] : table[c])(s.stream, args, d_q + off, d_aux ? d_aux + off : nullptr, counts[c]);
+        e = hipGetLastError();
+        off += counts[c];
+    }
+    if (e != hipSuccess) {
+        nbx_set_error("diagonal / column launches -> %s", hipGetErrorString(e));
+        rc = NBX_E_HIP;
+    }
+    (void)hipFreeAsync(d_q, s.stream);
+    return rc;
+}
+
+int session_diagonal(Session& s, double* d_diag) {
+    ColumnLists& l = s.lists;
+    for (int64_t& c : l.counts) c = 0;
+    l.quartets.clear();
+    l.aux.clear();
+    // class (l, l) after class: the pairs are few, two passes over them per class are nothing
+    for (int lab = 0; lab < NLP; ++lab)
+        for (size_t ij = 0; ij < s.eng.pairs.size(); ++ij) {
+            const Pair& pr = s.eng.pairs[ij];
+            if (pr.lab != lab || !quartet_survives(pr, pr, s.cutoff)) continue;
+            ++l.counts[lab * NLP + lab];
+            l.quartets.push_back(make_uint2(unsigned(ij), unsigned(ij)));
+        }
+    const size_t n = size_t(s.eng.nao);
+    return run_lists(s, LAUNCH_DIAG, true, l.counts, l.quartets.data(), nullptr, l.quartets.size(), d_diag, n * n, nullptr, 0,
+                     nullptr);
+}
+
+int session_columns(Session& s, int npair, const int64_t* sel, double* d_cols, int* d_col_pq) {
+    build_column_lists(s.eng, npair, sel, s.cutoff, s.lists);
+    const ColumnLists& l = s.lists;
+    const size_t n = size_t(s.eng.nao);
+    return run_lists(s, LAUNCH_COLUMN, false, l.counts, l.quartets.data(), l.aux.data(), l.quartets.size(), d_cols,
+                     size_t(l.ncols) * n * n, l.col_pq.data(), size_t(l.ncols), d_col_pq);
+}
+
+}  // namespace nbx_eri
+
+namespace {
+const char* const SHELL_TEXT = "%s: invalid shells (angular momentum 0 .. %d, nfunc = 2l+1 or (l+1)(l+2)/2)";
+}
+
+extern "C" int nbx_eri_diagonal(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc,
+                                const double* centres, const double* exps, const double* coefs, const double* sph,
+                                double cutoff, double* d_diag) {
+    NBX_CHECK_ARG(ctx != nullptr);
+    NBX_CHECK_ARG(d_diag != nullptr);
+    nbx_eri::Session s;
+    int rc = nbx_eri::session_open(ctx, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, s);
+    if (rc == NBX_E_INVALID) nbx_set_error(SHELL_TEXT, "nbx_eri_diagonal", DEV_LMAX);
+    if (rc != NBX_OK) return rc;
+    rc = nbx_eri::session_diagonal(s, d_diag);
+    nbx_eri::session_close(s);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == NBX_OK) rc = NBX_E_HIP;  // the lists die with this call
+    return rc;
+}
+
+extern "C" int nbx_eri_columns(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc,
+                               const double* centres, const double* exps, const double* coefs, const double* sph,
+                               double cutoff, int npair, const int* ia, const int* ib, double* d_cols) {
+    NBX_CHECK_ARG(ctx != nullptr);
+    NBX_CHECK_ARG(d_cols != nullptr);
+    NBX_CHECK_ARG(npair >= 0 && (npair == 0 || (ia != nullptr && ib != nullptr)));
+    for (int k = 0; k < npair; ++k)
+        if (ib[k] < 0 || ia[k] < ib[k] || ia[k] >= nshell) {
+            nbx_set_error("nbx_eri_columns: shell pair %d is (%d, %d); %d > ia >= ib >= 0 is required", k, ia[k], ib[k], nshell);
+            return NBX_E_INVALID;
+        }
+    nbx_eri::Session s;
+    int rc = nbx_eri::session_open(ctx, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, s);
+    if (rc == NBX_E_INVALID) nbx_set_error(SHELL_TEXT, "nbx_eri_columns", DEV_LMAX);
+    if (rc != NBX_OK) return rc;
+    std::vector<int64_t> sel(size_t(npair > 0 ? npair : 0));
+    for (int k = 0; k < npair; ++k) sel[k] = int64_t(ia[k]) * (ia[k] + 1) / 2 + ib[k];
+    rc = nbx_eri::session_columns(s, npair, sel.data(), d_cols, nullptr);
+    nbx_eri::session_close(s);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == NBX_OK) rc = NBX_E_HIP;  // the lists die with this call
     return rc;
 }
 

@@ -542,6 +542,13 @@ def two_electron_device(basis: Basis, backend, cutoff: float = 1e-16):
     return backend.eri(basis, cutoff=cutoff)
 
 
+def cholesky_device(basis: Basis, backend, tol: float = 1e-8, max_rank: int | None = None, cutoff: float = 1e-16):
+    """The Cholesky factor B (rank, nao, nao) of (pq|rs) as a DEVICE tensor, (pq|rs) = sum_L B[L, p, q] B[L, r, s] within
+    ``tol`` on every element (``nbx_eri_cholesky``, csrc/eri_cd.hip): what ``two_electron_device`` computes, in the form
+    the GEMM-shaped J/K reads, for molecules whose dense tensor does not fit.  Shells of l <= 2."""
+    return backend.eri_cholesky(basis, tol=tol, max_rank=max_rank, cutoff=cutoff)
+
+
 def molecule_integrals(xyz: str, basis: str = "sto-3g", unit: str = "angstrom", cart: bool = False,
                        engine: str = "native") -> dict:
     """Everything the embedding driver needs of a molecule: S, hcore = T + V, (pq|rs), e_nuc, the

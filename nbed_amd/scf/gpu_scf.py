@@ -106,9 +106,12 @@ class _GpuSCF:
     """Shared machinery: device-resident S, hcore, (pq|rs) (possibly a row slab)."""
 
     def __init__(self, mol: Mole, ovlp, hcore, eri=None, backend=None, shards: Shards | None = None,
-                 eri_packed=None):
+                 eri_packed=None, eri_factor=None):
         """``eri_packed``: the packed J/K copy of the same slab (``eri_packed_device()`` of another
-        object over the same integrals), so that objects sharing a molecule share it."""
+        object over the same integrals), so that objects sharing a molecule share it.
+        ``eri_factor``: instead of the tensor, a device (naux, N, N) factor with (pq|rs) = sum_L B[L, p, q] B[L, r, s]
+        (``HipBackend.eri_cholesky``); J/K then come from ``backend.jk_factor`` and the loops run step by step, since the
+        one-call-per-cycle paths read the tensor.  Single rank only."""
         self.be = backend if backend is not None else get_backend()
         self.mol = mol
         self._s_h = np.asarray(ovlp, dtype=np.float64)
@@ -123,7 +126,18 @@ class _GpuSCF:
                 raise ValueError(
                     f"ERI slab has shape {tuple(eri.shape)}, expected {(self.shards.size, nao, nao, nao)}"
                 )
+        if eri_factor is not None:
+            if eri is not None or eri_packed is not None:
+                raise ValueError("eri_factor excludes eri and eri_packed: give the tensor or its factor, not both")
+            if self.shards.world != 1 or self.shards.size != nao:
+                raise ValueError("eri_factor is single rank only: the decomposition is not split over row slabs")
+            eri_factor = self.be.asarray(eri_factor)
+            if eri_factor.ndim != 3 or tuple(eri_factor.shape[1:]) != (nao, nao):
+                raise ValueError(f"eri_factor has shape {tuple(eri_factor.shape)}, expected (naux, {nao}, {nao})")
+            if not hasattr(self.be, "jk_factor"):
+                raise ValueError("this backend has no jk_factor: it cannot run on a factor of the integrals")
         self._eri_d = eri
+        self._eri_factor_d = eri_factor
         self._eri_packed_d = eri_packed  # 4-fold packed copy of the slab for the J/K kernel, made on first use
         self._x_d = None  # S^-1/2, built on first use
         self.mo_coeff = None
@@ -186,6 +200,8 @@ class _GpuSCF:
         reuse it.  None when it does not apply (row-slab object, backend without it, too large)."""
         be = self.be
         nao = self._s_h.shape[0]
+        if self._eri_factor_d is not None:
+            return None
         shared = getattr(self, "_eri_shared", None)  # set by a provider whose objects share one molecule
         if getattr(self, "_eri_rs_d", None) is None and shared is not None:
             self._eri_rs_d = shared.get("rs")
@@ -203,6 +219,8 @@ class _GpuSCF:
         tiles q <= p of this rank's slab and return full-size partial matrices, summed over ranks
         by one all-reduce; a backend without them computes plain row slabs and all-gathers them."""
         be, sh = self.be, self.shards
+        if self._eri_factor_d is not None:
+            return be.jk_factor(self._eri_factor_d, dm_d)
         packed = self.eri_packed_device()
         if packed is not None:
             return sh.all_reduce(be, be.jk_packed(packed, dm_d, sh.lo, sh.hi))
@@ -345,7 +363,9 @@ class GpuUHF(_GpuSCF, UHF):
         be = self.be
         patched = any(k in vars(self) for k in ("get_veff", "get_occ", "make_rdm1", "get_fock"))
         if not patched and self._device_kernel_ok:
-            if hasattr(be, "mu_cycle") and os.environ.get("NBED_CYCLE_CALL", "1") != "0":
+            # (an object on a factor of the integrals takes the step-by-step loop: nbx_mu_cycle reads the tensor)
+            if (hasattr(be, "mu_cycle") and os.environ.get("NBED_CYCLE_CALL", "1") != "0"
+                    and self._eri_factor_d is None):
                 return self._kernel_cycle_calls(dm0)
             if all(hasattr(be, a) for a in ("huz_cycle_scalars_async", "density_occ", "vo_sumsq", "async_to_host")):
                 return self._kernel_device(dm0)
@@ -676,8 +696,8 @@ class GpuUKS(GpuUHF, UKS):
     _device_kernel_ok = False
 
     def __init__(self, mol, ovlp, hcore, eri=None, backend=None, shards=None, xc="hf", hyb=1.0, xc_provider=None,
-                 eri_packed=None):
-        super().__init__(mol, ovlp, hcore, eri, backend=backend, shards=shards, eri_packed=eri_packed)
+                 eri_packed=None, eri_factor=None):
+        super().__init__(mol, ovlp, hcore, eri, backend=backend, shards=shards, eri_packed=eri_packed, eri_factor=eri_factor)
         self.xc = xc
         self.hyb = float(hyb)
         self.xc_provider = xc_provider

@@ -304,8 +304,10 @@ def _huzinaga_scf(scf_method, embedding_potential, dm_environment_occupied, dm_e
     # Same kernels, order and operands as the step-by-step path below: bit-identical results.  Every size
     # (packed J/K kernel, or the symmetric one on the dense tensor) and every world size: over several ranks
     # the cycle is two calls around the all-reduce of the J/K partials (nbx_huz_cycle_jk / _post).
+    # (an object built on a factor of the integrals, ``eri_factor=``, has no tensor for nbx_huz_cycle to read)
     use_cycle_call = (lookahead and ds_virt is None and hasattr(be, "huz_cycle") and sh is not None
-                      and os.environ.get("NBED_CYCLE_CALL", "1") != "0")
+                      and os.environ.get("NBED_CYCLE_CALL", "1") != "0"
+                      and getattr(scf_method, "_eri_factor_d", None) is None)
     if not use_cycle_call:
         warm["purify"] = False  # (nbx_huz_cycle mode 2 only: the step-by-step path always solves the eigenproblem)
     if history is not None and hasattr(history, "info"):
