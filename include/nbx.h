@@ -842,6 +842,29 @@ int nbx_eri_cholesky(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim,
  * nbed/driver.py:155-191 has no counterpart of it): steps taken and columns (pq|m) computed.                 */
 int nbx_eri_cholesky_steps(int64_t* steps, int64_t* columns);
 
+/* ------------------------------------------------------------------ four-index transform from a factor
+ * The three ao2mo.kernel calls of nbed/ham_builder.py:127-133 (aaaa, bbbb, aabb; C1 = C2 and C3 = C4 in each) computed
+ * from the factor of nbx_eri_cholesky instead of the N^4 tensor (csrc/ao2mo_factor.hip):
+ *   M_L^x = C_x^T B_L C_x,   (ij|kl)_xy = sum_L M_L^x[i][j] M_L^y[k][l].
+ *   d_b          (naux, nao, nao) DEVICE, every slice symmetric; naux >= 1
+ *   nset         1 (one matrix d_ca: one block d_aaaa; d_cb, d_bbbb, d_aabb NULL) or 2 (aaaa, bbbb, aabb)
+ *   d_ca, d_cb   (nao, n) row-major with leading dimensions ldca, ldcb >= n (column slices of a wider matrix are fine)
+ *   d_aaaa ...   (n, n, n, n) chemist order, every element written; (ij|kl), (ji|kl), (ij|lk), (ji|lk) are the same double
+ *   d_work       nbx_ao2mo_factor_worksize() bytes: the packed half transform P and one (npair x npair) product,
+ *                npair = n (n + 1) / 2.  0 from the worksize call = arguments the transform refuses.
+ * Stages: nbx_ao2mo_factor_half (P[x][L][i (i + 1) / 2 + j] = M_L^x[i][j], j <= i: (nset, naux, npair), the intermediate
+ * B_L C kept on chip, fp64 MFMA), nbx_gemm 'T','N' over L, nbx_ao2mo_factor_expand (out[i][j][k][l] =
+ * G[pair(i,j)][pair(k,l)] of an (npair x npair) matrix G, a copy).  No atomics, fixed summation order: two calls give the
+ * same bits.  NBX_E_UNSUPPORTED for n > 361 (more than 65535 pairs, as nbx_ao2mo_pair_sym); NBX_E_INVALID for naux < 1
+ * and bad shapes, NBX_E_NOMEM for a short workspace: a refused call writes nothing.                                  */
+size_t nbx_ao2mo_factor_worksize(int64_t nao, int64_t naux, int64_t n, int64_t nset);
+int nbx_ao2mo_factor(nbx_ctx* ctx, int64_t nao, int64_t naux, const double* d_b, int64_t nset, const double* d_ca,
+                     int64_t ldca, const double* d_cb, int64_t ldcb, int64_t n, double* d_aaaa, double* d_bbbb,
+                     double* d_aabb, void* d_work, size_t work_bytes);
+int nbx_ao2mo_factor_half(nbx_ctx* ctx, int64_t nao, int64_t naux, const double* d_b, int64_t nset, const double* d_ca,
+                          int64_t ldca, const double* d_cb, int64_t ldcb, int64_t n, double* d_p);
+int nbx_ao2mo_factor_expand(nbx_ctx* ctx, int64_t n, const double* d_g, double* d_out);
+
 /* ------------------------------------------------------------------ coupled cluster (csrc/ccsd.hip)
  * What surrounds the GEMMs of a spin-orbital CCSD (nbed_amd/ccsd_gpu.py): the reference runs PySCF's
  * cc.CCSD on the embedded object (nbed/driver.py:1105-1135); here the amplitude equations of

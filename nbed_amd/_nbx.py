@@ -196,6 +196,11 @@ SIGNATURES = {
     "nbx_eri_cholesky": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_int64, _P, POINTER(c_int64),
                                  POINTER(c_double)]),
     "nbx_eri_cholesky_steps": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
+    "nbx_ao2mo_factor_worksize": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "nbx_ao2mo_factor": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P, _P, _P, _P,
+                                 c_size_t]),
+    "nbx_ao2mo_factor_half": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P]),
+    "nbx_ao2mo_factor_expand": (c_int, [_P, c_int64, _P, _P]),
     "nbx_huz_cycle": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                               c_int, _P, _P]),
     "nbx_huz_cycle_jk": (c_int, [_P, POINTER(HuzState), _P]),

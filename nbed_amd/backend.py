@@ -1404,6 +1404,89 @@ class HipBackend:
                    self._p(out), self._p(c5), n5, self._p(c6), n6, self._p(out2), self._p(work), work.numel())
         return (out, out2) if pair else out
 
+    # ---- the transform from a factor of the integrals (csrc/ao2mo_factor.hip)
+    @staticmethod
+    def _factor_coef(name, c, nao):
+        """(tensor, leading dimension) of an (nao, n) coefficient matrix; a column slice of a wider row-major matrix is
+        passed as it is."""
+        if c.dim() != 2 or int(c.shape[0]) != nao or int(c.shape[1]) < 1:
+            raise ValueError(f"ao2mo_factor: {name} has shape {tuple(c.shape)}, expected ({nao}, n >= 1)")
+        if c.stride(1) != 1 or c.stride(0) < c.shape[1]:
+            c = c.contiguous()
+        return c, int(c.stride(0))
+
+    def _factor_args(self, b, ca, cb):
+        if b.dim() != 3 or b.shape[1] != b.shape[2] or int(b.shape[0]) < 1:
+            raise ValueError(f"ao2mo_factor: factor of shape {tuple(b.shape)}, expected (naux >= 1, N, N)")
+        b = b.contiguous()
+        nao = int(b.shape[1])
+        ca, ldca = self._factor_coef("ca", ca, nao)
+        cb, ldcb = self._factor_coef("cb", cb, nao) if cb is not None else (None, 0)
+        if cb is not None and cb.shape[1] != ca.shape[1]:
+            raise ValueError(f"ao2mo_factor: {ca.shape[1]} alpha but {cb.shape[1]} beta orbitals")
+        return b, nao, int(b.shape[0]), ca, ldca, cb, ldcb, int(ca.shape[1])
+
+    def ao2mo_factor_half(self, b, ca, cb=None, half: str = "fused"):
+        """Stage 1 of ``ao2mo_factor``: P (nset, naux, n (n + 1) / 2) with P[x, L, i (i + 1) / 2 + j] = (C_x^T B_L C_x)[i, j],
+        j <= i.  ``half="fused"``: nbx_ao2mo_factor_half (B_L C stays on chip); ``"gemm"``: two batched nbx_gemm calls per
+        slab of L through a workspace, then packed -- the cross-check and the timing comparison of the fused kernel."""
+        b, nao, naux, ca, ldca, cb, ldcb, n = self._factor_args(b, ca, cb)
+        nset, npair = (1 if cb is None else 2), n * (n + 1) // 2
+        p = self.empty((nset, naux, npair))
+        if half == "fused":
+            self._call("nbx_ao2mo_factor_half", nao, naux, self._p(b), nset, self._p(ca), ldca, self._p(cb), ldcb, n, self._p(p))
+            return p
+        if half != "gemm":
+            raise ValueError(f"ao2mo_factor: half={half!r}, expected 'fused' or 'gemm'")
+        chunk = max(1, min(naux, self.JK_FACTOR_CHUNK_DOUBLES // (nao * max(nao, n))))
+        nbytes = 8 * chunk * (nao * n + n * n)
+        work = self._workspace("ao2mo_factor_gemm", nbytes)[:nbytes].view(self.torch.float64)
+        t, m = work[: chunk * nao * n], work[chunk * nao * n: chunk * (nao * n + n * n)]
+        tri = self.torch.tril_indices(n, n, device=self.device)
+        tri = tri[0] * n + tri[1]  # (row-major lower triangle: i (i + 1) / 2 + j in order)
+        for x, (c, ld) in enumerate(((ca, ldca), (cb, ldcb))[:nset]):
+            for l0 in range(0, naux, chunk):
+                nl = min(chunk, naux - l0)
+                self.gemm_raw("N", "N", nao, n, nao, 1.0, b[l0:], nao, nao * nao, c, ld, 0, 0.0, t, n, nao * n, nl)
+                self.gemm_raw("T", "N", n, n, nao, 1.0, c, ld, 0, t, n, nao * n, 0.0, m, n, n * n, nl)
+                p[x, l0:l0 + nl] = m[: nl * n * n].view(nl, n * n)[:, tri]
+        return p
+
+    def ao2mo_factor_expand(self, g, n: int):
+        """(n, n, n, n) chemist-order block out[i, j, k, l] = g[pair(i, j), pair(k, l)] of an (npair, npair) matrix
+        (nbx_ao2mo_factor_expand: a copy, no arithmetic)."""
+        npair = n * (n + 1) // 2
+        if tuple(g.shape) != (npair, npair) or not g.is_contiguous():
+            raise ValueError(f"ao2mo_factor_expand: g of shape {tuple(g.shape)}, expected a contiguous ({npair}, {npair})")
+        out = self.empty((n, n, n, n))
+        self._call("nbx_ao2mo_factor_expand", n, self._p(g), self._p(out))
+        return out
+
+    def ao2mo_factor(self, b, ca, cb=None, half: str = "fused"):
+        """The chemist-order MO blocks from the factor ``b`` (naux, N, N) of (pq|rs) (``eri_cholesky``), the N^4 tensor
+        never formed: (C_a C_a|C_a C_a) for one coefficient matrix, (aaaa, bbbb, aabb) for two (nbx_ao2mo_factor).
+        ``ca`` / ``cb``: (N, n) device matrices, column slices allowed.  ``half``: how stage 1 runs
+        (``ao2mo_factor_half``); the results of the two settings agree to rounding."""
+        b, nao, naux, ca, ldca, cb, ldcb, n = self._factor_args(b, ca, cb)
+        nset, npair = (1 if cb is None else 2), n * (n + 1) // 2
+        if half == "fused":
+            nbytes = int(self.lib.nbx_ao2mo_factor_worksize(nao, naux, n, nset))
+            if nbytes == 0:
+                raise ValueError(f"ao2mo_factor: n = {n} orbitals on naux = {naux} vectors is not supported (n <= 361)")
+            work = self._workspace("ao2mo_factor", nbytes)
+            outs = [self.empty((n, n, n, n)) for _ in range(1 if nset == 1 else 3)]
+            self._call("nbx_ao2mo_factor", nao, naux, self._p(b), nset, self._p(ca), ldca, self._p(cb), ldcb, n,
+                       self._p(outs[0]), self._p(outs[1] if nset == 2 else None), self._p(outs[2] if nset == 2 else None),
+                       self._p(work), work.numel())
+            return outs[0] if nset == 1 else tuple(outs)
+        p = self.ao2mo_factor_half(b, ca, cb, half=half)
+        g = self._workspace("ao2mo_factor_g", 8 * npair * npair)[: 8 * npair * npair].view(self.torch.float64).view(npair, npair)
+        outs = []
+        for x, y in ((0, 0),) if nset == 1 else ((0, 0), (1, 1), (0, 1)):
+            self.gemm_raw("T", "N", npair, npair, naux, 1.0, p[x], npair, 0, p[y], npair, 0, 0.0, g, npair, 0, 1)
+            outs.append(self.ao2mo_factor_expand(g, n))
+        return outs[0] if nset == 1 else tuple(outs)
+
     def ao2mo_synth(self, nao: int, c1, c2, c3, c4, r0: int = 0, r1: int | None = None, seed: int = 20250829):
         """Streamed transform of the synthetic ERI (never stored); partial sum over r in [r0,r1)."""
         n1, n2, n3, n4 = c1.shape[1], c2.shape[1], c3.shape[1], c4.shape[1]

@@ -132,6 +132,7 @@ class _TaggedVeff(np.ndarray):
 # on the host.
 AUTO_ERI_ON_DEVICE = True
 AUTO_ERI_MIN_NAO = 48
+CHOLESKY_TOL_MIN = 1e-12  # what nbx_eri_cholesky accepts (include/nbx.h)
 
 
 class _DeviceRouteIntegrals(dict):
@@ -157,10 +158,15 @@ class BuiltinHFProvider:
     exchange-correlation from the host-side quadrature
     (``XCProvider``), Coulomb and exact exchange from libnbx (``GpuUKS`` / ``GpuUHF``)."""
 
-    def __init__(self, backend=None, xc_grid: tuple[int, int] | None = None, eri_engine: str | None = None):
+    def __init__(self, backend=None, xc_grid: tuple[int, int] | None = None, eri_engine: str | None = None,
+                 cholesky_tol: float | None = None):
         """``eri_engine``: where (pq|rs) is computed -- "host" (``nbx_host_eri`` and an upload of the tensor), "device"
         (``nbx_eri_device``: shells of l <= 2, a backend with ``eri``; raises otherwise) or "auto" (the device where it
         can serve and the molecule has ``AUTO_ERI_MIN_NAO`` functions or more, the host otherwise); None reads ``NBED_ERI_ENGINE``, default "auto".
+        "cholesky": the tensor is never formed -- its pivoted Cholesky factor (``nbx_eri_cholesky``: shells of l <= 2, a
+        backend with ``eri_cholesky``; raises otherwise) reproduces every (pq|rs) within ``cholesky_tol`` (None reads
+        ``NBED_CHOLESKY_TOL``, default 1e-8; at least 1e-12), every SCF object of the molecule runs on it
+        (``eri_factor=``) and ``HamiltonianBuilder`` transforms it (``ao2mo_factor``).  ``auto`` never picks it.
         ``xc_grid``: (radial points per heavy atom, polar angles) of the exchange-correlation quadrature, or
         ("lebedev", level) for the Treutler-Ahlrichs x pruned-Lebedev construction PySCF documents as its default
         (``nbed_amd.xc.build_grid``; None = that construction at its default level 3, which needs SciPy >= 1.15 for
@@ -171,9 +177,17 @@ class BuiltinHFProvider:
         self._cache = {}
         self.xc_grid = xc_grid
         mode = eri_engine if eri_engine is not None else os.environ.get("NBED_ERI_ENGINE", "auto")
-        if mode not in ("auto", "host", "device"):
-            raise NbedDriverError(f"NBED_ERI_ENGINE={mode!r}: expected 'auto', 'host' or 'device'")
+        if mode not in ("auto", "host", "device", "cholesky"):
+            raise NbedDriverError(f"NBED_ERI_ENGINE={mode!r}: expected 'auto', 'host' or 'device', or 'cholesky'")
         self.eri_engine = mode
+        tol = cholesky_tol if cholesky_tol is not None else os.environ.get("NBED_CHOLESKY_TOL", "1e-8")
+        try:
+            tol = float(tol)
+        except (TypeError, ValueError):
+            raise NbedDriverError(f"NBED_CHOLESKY_TOL={tol!r}: expected a number of at least {CHOLESKY_TOL_MIN:g}") from None
+        if not (np.isfinite(tol) and tol >= CHOLESKY_TOL_MIN):
+            raise NbedDriverError(f"NBED_CHOLESKY_TOL={tol!r}: expected a number of at least {CHOLESKY_TOL_MIN:g}")
+        self.cholesky_tol = tol
 
     @staticmethod
     def supports(config: NbedConfig) -> bool:
@@ -195,12 +209,13 @@ class BuiltinHFProvider:
             else:
                 ints = _DeviceRouteIntegrals(integrals.molecule_integrals(config.geometry, str(config.basis), str(config.unit),
                                                                           engine="native-1e"))
-                ints.fetch_eri = lambda: self._host_eri(config, ints["basis"])
+                if self.eri_engine != "cholesky":  # (a cholesky run has no tensor to hand out: ints["eri"] is a KeyError)
+                    ints.fetch_eri = lambda: self._host_eri(config, ints["basis"])
                 self._cache[key] = ints
         return self._cache[key]
 
     def _eri_route(self, config: NbedConfig) -> str:
-        """"host" or "device" for this molecule on the provider's backend (``eri_engine``)."""
+        """"host", "device" or "cholesky" for this molecule on the provider's backend (``eri_engine``)."""
         from . import integrals
 
         if self.eri_engine == "host":
@@ -215,6 +230,14 @@ class BuiltinHFProvider:
             return "device" if lmax <= 2 and basis.nao >= AUTO_ERI_MIN_NAO else "host"
         if be is None:
             be = get_backend()
+        if self.eri_engine == "cholesky":
+            if not hasattr(be, "eri_cholesky"):
+                raise NbedDriverError(f"eri_engine='cholesky': the {getattr(be, 'name', type(be).__name__)} backend has no "
+                                      "device integral engine")
+            if lmax > 2:
+                raise NbedDriverError(f"eri_engine='cholesky': {config.basis} has shells of l = {lmax}; the device engine "
+                                      "covers l <= 2 (use 'host' or 'auto')")
+            return "cholesky"
         if not hasattr(be, "eri"):
             raise NbedDriverError(f"eri_engine='device': the {getattr(be, 'name', type(be).__name__)} backend has no "
                                   "device integral engine")
@@ -243,6 +266,15 @@ class BuiltinHFProvider:
 
         be = backend if backend is not None else (self._be if self._be is not None else get_backend())
         key = ("eri_device", id(be), config.geometry, str(config.basis).lower(), str(config.unit))
+        if self.eri_engine == "cholesky":
+            # one factor per (backend, molecule); no donor and no packed copies: there is no tensor to pack
+            if not hasattr(be, "eri_cholesky"):
+                raise NbedDriverError(f"eri_engine='cholesky': the {getattr(be, 'name', type(be).__name__)} backend has no "
+                                      "device integral engine")
+            key = ("eri_factor", id(be), config.geometry, str(config.basis).lower(), str(config.unit))
+            if key not in self._cache:
+                self._cache[key] = {"factor": be.eri_cholesky(self._integrals(config)["basis"], tol=self.cholesky_tol), "be": be}
+            return {"eri_factor": self._cache[key]["factor"], "backend": be}
         if key not in self._cache:
             ints = self._integrals(config)
             if "eri" in ints or not hasattr(be, "eri"):  # the host route, or a cache entry that holds a host tensor

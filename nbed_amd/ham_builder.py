@@ -13,7 +13,8 @@ n_frozen_core=0, n_frozen_virt=0).build() -> (float, h1 (2n,2n), h2 (2n,2n,2n,2n
 
 The AO (pq|rs) comes from the SCF object: ``eri_device()`` for this package's objects,
 ``mol.intor('int2e')`` for a PySCF object (the reference recomputes them inside
-``ao2mo.kernel(mol, ...)``).
+``ao2mo.kernel(mol, ...)``).  An object built on a factor of the integrals (``eri_factor_device()``) is
+transformed from the factor (``backend.ao2mo_factor``, nbx_ao2mo_factor) and is never asked for (pq|rs).
 """
 
 from __future__ import annotations
@@ -45,6 +46,25 @@ def _ao_eri_device(scf_method, be):
     if hasattr(mol, "intor"):
         return be.asarray(np.asarray(mol.intor("int2e")))
     raise HamiltonianBuilderError("cannot obtain AO two-electron integrals from this SCF object")
+
+
+def _ao_eri_factor_device(scf_method, be, shards):
+    """The (naux, N, N) factor of an SCF object built on one (``eri_factor_device()``), else None."""
+    accessor = getattr(scf_method, "eri_factor_device", None)
+    factor = accessor() if accessor is not None else None
+    if factor is None:
+        return None
+    if not hasattr(be, "ao2mo_factor"):
+        raise HamiltonianBuilderError(
+            f"this SCF object holds a factor of (pq|rs), and the {getattr(be, 'name', type(be).__name__)} backend has no "
+            "ao2mo_factor to transform it"
+        )
+    own = getattr(scf_method, "shards", None)
+    if (shards is not None and shards.world > 1) or (own is not None and own.world > 1):
+        raise HamiltonianBuilderError(
+            "the four-index transform from a factor of (pq|rs) is single rank only: it is not split over an outer-index slab"
+        )
+    return factor
 
 
 class HamiltonianBuilder:
@@ -87,6 +107,9 @@ class HamiltonianBuilder:
         layout, nbed/ham_builder.py:119-124) bbaa; ``blocks`` = 3 neither forms nor allocates the fourth."""
         be = self.be
         c = self.scf_method.mo_coeff
+        factor = _ao_eri_factor_device(self.scf_method, be, self.shards)
+        if factor is not None:
+            return self._two_body_from_factor(factor, blocks)
         if self._restricted:
             eri = _ao_eri_device(self.scf_method, be)
             c_d = be.asarray(np.asarray(c))
@@ -113,6 +136,26 @@ class HamiltonianBuilder:
         bbaa = be.transpose(aabb.reshape(n * n, n * n)).reshape(n, n, n, n)
         out = be.empty((4, n, n, n, n))
         for i, blk in enumerate((aaaa, bbbb, aabb, bbaa)):
+            out[i].copy_(be.chem_to_phys(blk))
+        return out
+
+    def _two_body_from_factor(self, factor, blocks: int):
+        """``_two_body_device`` for an SCF object built on a factor B of the integrals: the blocks come from
+        ``ao2mo_factor`` (sum_L M_L^x[i,j] M_L^y[k,l], M_L^x = C_x^T B_L C_x) and (pq|rs) is never asked for."""
+        be = self.be
+        c = self.scf_method.mo_coeff
+        if self._restricted:
+            block = be.chem_to_phys(be.ao2mo_factor(factor, be.asarray(np.asarray(c))))
+            return be.torch.stack([block] * blocks)
+        n_a, n_b = np.shape(c[0])[1], np.shape(c[1])[1]
+        if n_a != n_b:
+            raise HamiltonianBuilderError("Must localize the same number of alpha and beta orbitals.")
+        n = n_a
+        chem = be.ao2mo_factor(factor, be.asarray(np.asarray(c[0])), be.asarray(np.asarray(c[1])))
+        if blocks == 4:  # (bb|aa)[i,j,k,l] = (aa|bb)[k,l,i,j], as in the dense route
+            chem = (*chem, be.transpose(chem[2].reshape(n * n, n * n)).reshape(n, n, n, n))
+        out = be.empty((blocks, n, n, n, n))
+        for i, blk in enumerate(chem):
             out[i].copy_(be.chem_to_phys(blk))
         return out
 

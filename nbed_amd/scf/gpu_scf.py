@@ -172,6 +172,11 @@ class _GpuSCF:
             raise ValueError("this SCF object was built without two-electron integrals")
         return self._eri_d
 
+    def eri_factor_device(self):
+        """The device (naux, N, N) factor this object was built on (``eri_factor=``), or None: what
+        ``HamiltonianBuilder`` transforms instead of ``eri_device()``."""
+        return self._eri_factor_d
+
     def x_device(self):
         if self._x_d is None:
             # S^-1/2 (nbed/scf/huzinaga_scf.py:128) by GEMMs where the backend has the iteration
