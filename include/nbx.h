@@ -842,6 +842,27 @@ int nbx_eri_cholesky(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim,
  * nbed/driver.py:155-191 has no counterpart of it): steps taken and columns (pq|m) computed.                 */
 int nbx_eri_cholesky_steps(int64_t* steps, int64_t* columns);
 
+/* ------------------------------------------------------------------ potential of an MM environment (QM/MM)
+ * What qmmm.mm_charge(mf, coords, charges, radii) adds to get_hcore() of the objects the reference wraps
+ * (nbed/driver.py:171-180 global Kohn-Sham, :246-253 embedded HF), over the shells of nbx_host_eri:
+ *   V[mu][nu] = - sum_c q_c int mu(r) nu(r) erf(sqrt(zeta_c) |r - C_c|) / |r - C_c| dr,    zeta_c = 1 / radius_c^2,
+ * the potential of normalised Gaussian charges; zeta == NULL: point charges (int1e_nuc with the charges as nuclei).
+ *   q (ncharge), xyz (ncharge, 3; Bohr), zeta (ncharge, > 0, or NULL)   HOST arrays, finite
+ * nbx_host_mm_potential: shells of l <= 3, v_out (nao, nao) HOST, every element written (zeros for ncharge = 0),
+ * exactly symmetric, independent of nthreads (<= 0: all hardware threads); no primitive pair is screened.         */
+int nbx_host_mm_potential(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                          const double* exps, const double* coefs, const double* sph, int ncharge, const double* q,
+                          const double* xyz, const double* zeta, int nthreads, double* v_out);
+/* nbx_mm_potential (the same addition to get_hcore(), nbed/driver.py:171-180, 246-253, on the device; csrc/mm_potential.hip,
+ * DESIGN.md section 15): shells, cutoff, primitive screening (cutoff * 1e-4) and refusals as nbx_eri_diagonal
+ * (NBX_E_INVALID for l > 2); one upload of the charges.  v_device (nao, nao) DEVICE: every element written (exact zeros
+ * where all primitive pairs of a shell pair are screened out, and for ncharge = 0), exactly symmetric.  No atomics;
+ * the order of every sum depends on the shells and on ncharge alone: two calls give the same bits.  The call returns
+ * with the stream idle.                                                                                            */
+int nbx_mm_potential(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                     const double* exps, const double* coefs, const double* sph, double cutoff, int ncharge,
+                     const double* q, const double* xyz, const double* zeta, double* v_device);
+
 /* ------------------------------------------------------------------ four-index transform from a factor
  * The three ao2mo.kernel calls of nbed/ham_builder.py:127-133 (aaaa, bbbb, aabb; C1 = C2 and C3 = C4 in each) computed
  * from the factor of nbx_eri_cholesky instead of the N^4 tensor (csrc/ao2mo_factor.hip):

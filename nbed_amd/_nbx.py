@@ -196,6 +196,8 @@ SIGNATURES = {
     "nbx_eri_cholesky": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_int64, _P, POINTER(c_int64),
                                  POINTER(c_double)]),
     "nbx_eri_cholesky_steps": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
+    "nbx_host_mm_potential": (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P]),
+    "nbx_mm_potential": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_double, c_int, _P, _P, _P, _P]),
     "nbx_ao2mo_factor_worksize": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "nbx_ao2mo_factor": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P, _P, _P, _P,
                                  c_size_t]),

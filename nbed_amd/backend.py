@@ -585,6 +585,27 @@ class HipBackend:
                              f"{resid.value:.3e} after max_rank = {int(max_rank)} vectors")
         return buf[: int(rank.value)]
 
+    MM_CHUNK = 512  # charges of one workgroup of nbx_mm_potential (MM_CHUNK of csrc/mm_potential.hip)
+
+    def mm_potential(self, basis, coords, charges, zetas=None, cutoff: float = 1e-16):
+        """V_mm (nao, nao) of the MM charges ``charges`` (M,) at ``coords`` (M, 3; Bohr) with Gaussian exponents ``zetas``
+        (M,; None: point charges) as a device matrix, exactly symmetric, every element written (nbx_mm_potential):
+        ``integrals.mm_potential`` on the device, shells of l <= 2."""
+        arrays, ptrs = self._eri_shell_args(basis, "mm_potential")
+        coords = np.ascontiguousarray(np.asarray(coords, dtype=np.float64).reshape(-1, 3))
+        charges = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
+        if coords.shape[0] != charges.shape[0]:
+            raise ValueError(f"mm_potential: {coords.shape[0]} positions for {charges.shape[0]} charges")
+        if zetas is not None:
+            zetas = np.ascontiguousarray(np.asarray(zetas, dtype=np.float64).reshape(-1))
+            if zetas.shape != charges.shape:
+                raise ValueError(f"mm_potential: {zetas.shape[0]} exponents for {charges.shape[0]} charges")
+        ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        out = self.empty((basis.nao, basis.nao))
+        self._call("nbx_mm_potential", len(basis.shells), *ptrs, float(cutoff), len(charges), ptr(charges), ptr(coords),
+                   ptr(zetas), self._p(out))
+        return out
+
     def eri_class_ms(self) -> np.ndarray:
         """Milliseconds of each class launch (5, 5) of the last ``eri`` call made under ``profile(slots=[PROF_ERI])``."""
         ms = (c_double * _nbx.ERI_CLASSES)()

@@ -63,31 +63,6 @@ inline int lds_bytes_of(int lab, int lcd) { return int(LDS_BYTES[lab * NLP + lcd
 inline int wg_per_cu(int lab, int lcd) { return std::min(ERI_MAX_WG_PER_CU, ERI_LDS_PER_CU / lds_bytes_of(lab, lcd)); }
 inline int64_t grid_of(int lab, int lcd, int64_t count) { return std::min<int64_t>(count, int64_t(ERI_CUS) * wg_per_cu(lab, lcd)); }
 
-// BoysTable::eval
-template <int L>
-__device__ __forceinline__ void boys_eval(const double* __restrict__ tab, double t, double* out) {
-    if (t >= BoysTable::TMAX - 1.0) {
-        const double et = exp(-t);
-        out[0] = 0.5 * sqrt(M_PI / t);
-#pragma unroll
-        for (int m = 0; m < L; ++m) out[m + 1] = ((2 * m + 1) * out[m] - et) / (2.0 * t);
-        return;
-    }
-    const int i = int(t / BoysTable::STEP + 0.5);
-    const double d = i * BoysTable::STEP - t;
-    const double* row = tab + size_t(i) * (BoysTable::NORD + 1);
-    double acc = 0.0, pw = 1.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        acc += row[L + k] * pw;
-        pw *= d / (k + 1);
-    }
-    out[L] = acc;
-    const double et = exp(-t);
-#pragma unroll
-    for (int m = L; m > 0; --m) out[m - 1] = (2.0 * t * out[m] + et) / (2 * m - 1);
-}
-
 // The sinks of eri_class_kernel: where the spherical block of a quartet goes.
 constexpr int SINK_DENSE = 0;   // eight images into the (nao)^4 tensor
 constexpr int SINK_DIAG = 1;    // quartets (ij, ij): d[p][q] = d[q][p] = (pq|pq)

@@ -1,5 +1,6 @@
 // What eri.hip (the class kernel and its three sinks) offers to eri_cd.hip (the pivoted Cholesky decomposition): one
 // molecule's pair data, Boys table and index tables uploaded once, then any number of diagonal / column launches on it.
+// mm_potential.hip (the potential of MM charges) runs its own kernels on the same session and Boys evaluation.
 #pragma once
 
 #include "ints_md.h"
@@ -71,6 +72,32 @@ struct EriArgs {
     double pref0;         // 2 pi^(5/2)
     int nao;
 };
+
+// BoysTable::eval on the device (tab = BoysTable::f): F_0 .. F_L at t.  Shared by eri.hip and mm_potential.hip.
+template <int L>
+__device__ __forceinline__ void boys_eval(const double* __restrict__ tab, double t, double* out) {
+    using nbx_md::BoysTable;
+    if (t >= BoysTable::TMAX - 1.0) {
+        const double et = exp(-t);
+        out[0] = 0.5 * sqrt(M_PI / t);
+#pragma unroll
+        for (int m = 0; m < L; ++m) out[m + 1] = ((2 * m + 1) * out[m] - et) / (2.0 * t);
+        return;
+    }
+    const int i = int(t / BoysTable::STEP + 0.5);
+    const double d = i * BoysTable::STEP - t;
+    const double* row = tab + size_t(i) * (BoysTable::NORD + 1);
+    double acc = 0.0, pw = 1.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        acc += row[L + k] * pw;
+        pw *= d / (k + 1);
+    }
+    out[L] = acc;
+    const double et = exp(-t);
+#pragma unroll
+    for (int m = L; m > 0; --m) out[m - 1] = (2.0 * t * out[m] + et) / (2 * m - 1);
+}
 
 struct Session {
     nbx_md::Engine eng;

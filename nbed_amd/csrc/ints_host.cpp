@@ -344,3 +344,72 @@ extern "C" int nbx_host_dipole(int nshell, const int* ang, const int* nprim, con
     for (auto& th : pool) th.join();
     return NBX_OK;
 }
+
+// Potential of an MM environment in the AO basis (qmmm.mm_charge's addition to get_hcore(), nbed/driver.py:171-180,
+// 246-253): V[mu nu] = - sum_c q_c (mu nu | erf(sqrt(zeta_c) r_C) / r_C), the potential of normalised Gaussian charges of
+// exponent zeta_c (zeta == NULL: point charges).  Per primitive pair (p, P) the charges are summed into the Hermite
+// potential A_tuv = - sum_c q_c (1 + p / zeta_c)^(-1/2) R_tuv(rho_c, P - C_c), rho_c = p / (1 + p / zeta_c), and the
+// pair's Hermite densities contract A once: a charge costs one Boys evaluation and one recursion, no component loop.
+// Shell pairs over the thread pool; no primitive is screened; the result does not depend on nthreads.
+extern "C" int nbx_host_mm_potential(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                                     const double* exps, const double* coefs, const double* sph, int ncharge,
+                                     const double* q, const double* xyz, const double* zeta, int nthreads, double* v_out) {
+    if (nshell <= 0 || !ang || !nprim || !nfunc || !centres || !exps || !coefs || !sph || ncharge < 0 || !v_out ||
+        (ncharge > 0 && (!q || !xyz)))
+        return NBX_E_INVALID;
+    for (int c = 0; c < ncharge; ++c) {
+        if (!std::isfinite(q[c]) || !std::isfinite(xyz[3 * c]) || !std::isfinite(xyz[3 * c + 1]) || !std::isfinite(xyz[3 * c + 2]))
+            return NBX_E_INVALID;
+        if (zeta && !(zeta[c] > 0.0)) return NBX_E_INVALID;
+    }
+    Engine eng;
+    if (engine_shells(eng, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, LMAX) != NBX_OK) return NBX_E_INVALID;
+    for (int l = 0; l <= 2 * LMAX; ++l) eng.hidx[l] = HermIndex(l);
+    const int n = eng.nao;
+    const int64_t npair = int64_t(nshell) * (nshell + 1) / 2;
+    std::atomic<int64_t> next{0};
+    run_pool(pool_size(nthreads), [&] {
+        std::vector<double> rbuf(NCUBE * NCUBE * NCUBE), rtmp(NCUBE * NCUBE * NCUBE);
+        double pot[84], blk[100], ov[100];  // nherm(2 LMAX) Hermite orders
+        int off[84];
+        for (;;) {
+            const int64_t ij = next.fetch_add(1);
+            if (ij >= npair) break;
+            int ia = int((std::sqrt(8.0 * double(ij) + 1.0) - 1.0) / 2.0);
+            while (int64_t(ia) * (ia + 1) / 2 > ij) --ia;
+            while (int64_t(ia + 1) * (ia + 2) / 2 <= ij) ++ia;
+            const int ib = int(ij - int64_t(ia) * (ia + 1) / 2);
+            const Shell &sa = eng.shells[ia], &sb = eng.shells[ib];
+            Pair pr;
+            build_pair(sa, sb, ia, ib, 0.0, eng.hidx, pr);
+            const HermIndex& hi = eng.hidx[pr.lab];
+            for (int k = 0; k < pr.nh; ++k) off[k] = (hi.tuv[k][0] * NCUBE + hi.tuv[k][1]) * NCUBE + hi.tuv[k][2];
+            for (int k = 0; k < pr.nab; ++k) blk[k] = 0.0;
+            for (int i = 0; i < pr.nprim; ++i) {
+                const double p = pr.p[i];
+                for (int k = 0; k < pr.nh; ++k) pot[k] = 0.0;
+                for (int c = 0; c < ncharge; ++c) {
+                    const double s = 1.0 + (zeta ? p / zeta[c] : 0.0);
+                    hermite_r(pr.lab, p / s, pr.px[i] - xyz[3 * c], pr.py[i] - xyz[3 * c + 1], pr.pz[i] - xyz[3 * c + 2],
+                              eng.boys, rbuf.data(), rtmp.data());
+                    const double w = -q[c] / std::sqrt(s);
+                    for (int k = 0; k < pr.nh; ++k) pot[k] += w * rbuf[off[k]];
+                }
+                const double pref = 2.0 * M_PI / p;
+                const double* h = &pr.h[size_t(i) * pr.nab * pr.nh];
+                for (int a = 0; a < pr.nab; ++a) {
+                    double acc = 0.0;
+                    for (int k = 0; k < pr.nh; ++k) acc += h[size_t(a) * pr.nh + k] * pot[k];
+                    blk[a] += pref * acc;
+                }
+            }
+            block_to_ao(sa, sb, blk, ov);
+            for (int m = 0; m < sa.nsph; ++m)
+                for (int k = 0; k < sb.nsph; ++k) {
+                    const size_t r = size_t(sa.ao0 + m), c = size_t(sb.ao0 + k);
+                    v_out[r * n + c] = v_out[c * n + r] = ov[m * sb.nsph + k];
+                }
+        }
+    });
+    return NBX_OK;
+}

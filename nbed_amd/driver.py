@@ -133,6 +133,17 @@ class _TaggedVeff(np.ndarray):
 AUTO_ERI_ON_DEVICE = True
 AUTO_ERI_MIN_NAO = 48
 CHOLESKY_TOL_MIN = 1e-12  # what nbx_eri_cholesky accepts (include/nbx.h)
+# Which engine ``mm_engine="auto"`` takes for the MM potential where both can serve (a backend with ``mm_potential``, shells
+# of l <= 2): the device from this many (primitive pairs of the shell pairs ia >= ib) x (MM charges) on.  Measured by
+# tools/time_mm_potential.py on an MI355X against nbx_host_1e with the charges as its atoms on 16 threads, the only way to
+# such a matrix before (profiles/mm_potential/): the device call costs 0.9 ms (water / cc-pVDZ, 793
+# primitive pairs) to 2.9 ms (octane / 6-31G*, 18 750) whatever the number of charges -- pair data on the host, two
+# uploads, one synchronise -- and the host 2.4 us (water) to 49 us (octane) per charge.  Water: the host wins at 256
+# charges (0.99 against 1.08 ms, work 2.0e5), the device at 512 (1.26 against 1.48 ms, work 4.1e5); octane: the host at
+# 32 (2.38 against 2.88 ms, work 6.0e5), the device at 64 (3.01 against 3.85 ms, work 1.2e6).  1.2e6 is the smallest
+# measured work from which the device wins on both; at 65 536 charges it is 67 (water) and 468 (octane) times faster.
+AUTO_MM_ON_DEVICE = True
+AUTO_MM_MIN_WORK = 1_200_000
 
 
 class _DeviceRouteIntegrals(dict):
@@ -159,7 +170,7 @@ class BuiltinHFProvider:
     (``XCProvider``), Coulomb and exact exchange from libnbx (``GpuUKS`` / ``GpuUHF``)."""
 
     def __init__(self, backend=None, xc_grid: tuple[int, int] | None = None, eri_engine: str | None = None,
-                 cholesky_tol: float | None = None):
+                 cholesky_tol: float | None = None, mm_engine: str | None = None):
         """``eri_engine``: where (pq|rs) is computed -- "host" (``nbx_host_eri`` and an upload of the tensor), "device"
         (``nbx_eri_device``: shells of l <= 2, a backend with ``eri``; raises otherwise) or "auto" (the device where it
         can serve and the molecule has ``AUTO_ERI_MIN_NAO`` functions or more, the host otherwise); None reads ``NBED_ERI_ENGINE``, default "auto".
@@ -172,7 +183,15 @@ class BuiltinHFProvider:
         (``nbed_amd.xc.build_grid``; None = that construction at its default level 3, which needs SciPy >= 1.15 for
         ``scipy.integrate.lebedev_rule`` -- pass (n_rad, n_theta) for the product grid on an older SciPy).  Matrix elements of
         v_xc[D_act] between VIRTUAL orbitals converge much more slowly -- the active density of a SPADE partition
-        has near-nodal surfaces where the GGA potential is singular -- and need a finer grid."""
+        has near-nodal surfaces where the GGA potential is singular -- and need a finer grid.
+        ``mm_engine``: where the potential of the MM charges of a QM/MM run (``mm_coords`` / ``mm_charges`` /
+        ``mm_radii``) is computed -- "host" (``nbx_host_mm_potential``), "device" (``nbx_mm_potential``: shells of l <= 2,
+        a backend with ``mm_potential``; raises otherwise) or "auto" (the device where it can serve and the work,
+        primitive pairs x charges, reaches ``AUTO_MM_MIN_WORK``); None reads ``NBED_MM_ENGINE``, default "auto"."""
+        mm_mode = mm_engine if mm_engine is not None else os.environ.get("NBED_MM_ENGINE", "auto")
+        if mm_mode not in ("auto", "host", "device"):
+            raise NbedDriverError(f"NBED_MM_ENGINE={mm_mode!r}: expected 'auto', 'host' or 'device'")
+        self.mm_engine = mm_mode
         self._be = backend
         self._cache = {}
         self.xc_grid = xc_grid
@@ -195,8 +214,7 @@ class BuiltinHFProvider:
 
         from . import xc as xcmod
 
-        no_mm = None in [config.mm_charges, config.mm_coords, config.mm_radii]
-        return (str(config.xc_functional).lower().replace(" ", "") in xcmod.HYBRID_FRACTION and no_mm
+        return (str(config.xc_functional).lower().replace(" ", "") in xcmod.HYBRID_FRACTION
                 and integrals.supports(config.geometry, str(config.basis)))
 
     def _integrals(self, config: NbedConfig):
@@ -322,8 +340,70 @@ class BuiltinHFProvider:
             self._cache[key] = integrals.molecule_dipole(config.geometry, str(config.basis), str(config.unit))
         return self._cache[key]
 
+    def _mm_route(self, config: NbedConfig, basis, ncharge: int, backend=None):
+        """("host", None) or ("device", backend) for the MM potential of this molecule (``mm_engine``)."""
+        from . import integrals
+
+        if self.mm_engine == "host":
+            return "host", None
+        be = backend if backend is not None else self._be
+        lmax = integrals.max_ang(basis)
+        if self.mm_engine == "auto":
+            if not AUTO_MM_ON_DEVICE or be is None or not hasattr(be, "mm_potential") or lmax > 2:
+                return "host", None
+            nprim = [len(sh.exps) for sh in basis.shells]
+            work = sum(a * b for i, a in enumerate(nprim) for b in nprim[: i + 1]) * int(ncharge)
+            return ("device", be) if work >= AUTO_MM_MIN_WORK else ("host", None)
+        if be is None:
+            be = get_backend()
+        if not hasattr(be, "mm_potential"):
+            raise NbedDriverError(f"mm_engine='device': the {getattr(be, 'name', type(be).__name__)} backend has no "
+                                  "device integral engine")
+        if lmax > 2:
+            raise NbedDriverError(f"mm_engine='device': {config.basis} has shells of l = {lmax}; the device engine covers "
+                                  "l <= 2 (use 'host' or 'auto')")
+        return "device", be
+
+    def mm_route(self, config: NbedConfig, backend=None) -> str:
+        """"host" or "device": the engine this provider computes the configuration's MM potential with."""
+        from . import integrals
+
+        basis = integrals.Basis(integrals.parse_geometry(config.geometry, str(config.unit)), str(config.basis))
+        return self._mm_route(config, basis, len(config.mm_charges), backend)[0]
+
+    def _mm_terms(self, config: NbedConfig, backend=None):
+        """(V_mm (nao, nao) host matrix, e_mm) of the configuration's MM charges: what ``qmmm.mm_charge`` adds to
+        ``get_hcore()`` and to ``energy_nuc()`` (nbed/driver.py:171-180, 246-253).  Computed once per (molecule,
+        charges)."""
+        from . import integrals
+
+        coords, charges, radii = integrals.mm_environment(config.mm_coords, config.mm_charges, config.mm_radii, str(config.unit))
+        key = ("mm", config.geometry, str(config.basis).lower(), str(config.unit), coords.tobytes(), charges.tobytes(),
+               radii.tobytes())
+        if key not in self._cache:
+            atoms = integrals.parse_geometry(config.geometry, str(config.unit))
+            basis = integrals.Basis(atoms, str(config.basis))
+            route, be = self._mm_route(config, basis, len(charges), backend)
+            if route == "device":
+                v_mm = np.asarray(be.to_host(integrals.mm_potential_device(basis, be, coords, charges, radii)))
+            else:
+                v_mm = integrals.mm_potential_native(basis, coords, charges, radii)
+            self._cache[key] = (v_mm, integrals.mm_nuclear_energy(atoms, coords, charges), route)
+        return self._cache[key][:2]
+
+    def _with_mm(self, config: NbedConfig, run_qmmm: bool, backend=None):
+        """(hcore, energy_nuc override or None) of an SCF object of this molecule: with ``run_qmmm`` the core Hamiltonian
+        carries V_mm and ``energy_nuc()`` the nuclei-MM term; without it the cached hcore itself and no override."""
+        ints = self._integrals(config)
+        if not run_qmmm:
+            return ints["hcore"], None
+        v_mm, e_mm = self._mm_terms(config, backend)
+        e_nuc = float(ints["e_nuc"]) + float(e_mm)
+        return ints["hcore"] + v_mm, (lambda *args: e_nuc)
+
     def global_hf(self, config: NbedConfig):
-        """Converged global UHF (nbed/driver.py:106-124), on libnbx."""
+        """Converged global UHF (nbed/driver.py:106-124), on libnbx.  As in the reference, this object is NOT wrapped in
+        ``qmmm.mm_charge``: it never sees the MM field."""
         from .scf import GpuUHF
 
         ints = self._integrals(config)
@@ -354,27 +434,31 @@ class BuiltinHFProvider:
             self._cache[key] = xcmod.XCProvider(atoms, integrals.Basis(atoms, str(config.basis)), name, **grid)
         return self._cache[key]
 
-    def _uks(self, config: NbedConfig, mol, xc_functional: str, backend):
+    def _uks(self, config: NbedConfig, mol, xc_functional: str, backend, hcore=None):
         from . import xc as xcmod
         from .scf import GpuUKS
 
         ints = self._integrals(config)
-        return self._adopt(config, GpuUKS(mol, ints["S"], ints["hcore"], xc=str(xc_functional),
+        return self._adopt(config, GpuUKS(mol, ints["S"], ints["hcore"] if hcore is None else hcore, xc=str(xc_functional),
                                           hyb=xcmod.hybrid_fraction(xc_functional),
                                           xc_provider=self._xc_provider(config, xc_functional),
                                           **self._eri_kwargs(config, backend)))
 
     def global_ks(self, config: NbedConfig, run_qmmm: bool = False):
+        """Converged global Kohn-Sham object (nbed/driver.py:155-191).  With ``run_qmmm`` it is built on hcore + V_mm and
+        its ``energy_nuc()`` carries the nuclei-MM term, as the reference's ``qmmm.mm_charge`` wrapper does (:171-180)."""
         from .scf import GpuUHF
 
-        if run_qmmm or not self.supports(config):
+        if not self.supports(config):
             from . import xc as xcmod
 
             raise NbedDriverError(f"BuiltinHFProvider covers xc_functional in {sorted(xcmod.HYBRID_FRACTION)} ('pbeh' / "
-                                  "'pbe1pbe' is the functional also called PBE0), H/C/N/O in STO-3G, 6-31G(*), cc-pVDZ, "
-                                  "no QM/MM")
+                                  "'pbe1pbe' is the functional also called PBE0), H/C/N/O in STO-3G, 6-31G(*), cc-pVDZ")
+        hcore, energy_nuc = self._with_mm(config, run_qmmm, self._be)
         if str(config.xc_functional).lower() != "hf":
-            ks = self._uks(config, self.build_mol(config), config.xc_functional, self._be)
+            ks = self._uks(config, self.build_mol(config), config.xc_functional, self._be, hcore=hcore)
+            if energy_nuc is not None:
+                ks.energy_nuc = energy_nuc
             ks.conv_tol = config.convergence
             ks.max_cycle = config.max_dft_cycles
             ks.kernel()
@@ -396,24 +480,30 @@ class BuiltinHFProvider:
                 v.exc = -0.5 * float(np.einsum("xij,xji->", vk, dm3))
                 return v
 
-        ks = self._adopt(config, GlobalHF(self.build_mol(config), ints["S"], ints["hcore"],
-                                          **self._eri_kwargs(config, self._be)))
+        ks = self._adopt(config, GlobalHF(self.build_mol(config), ints["S"], hcore, **self._eri_kwargs(config, self._be)))
+        if energy_nuc is not None:
+            ks.energy_nuc = energy_nuc
         ks.conv_tol = config.convergence
         ks.max_cycle = config.max_dft_cycles
         ks.kernel()
         return ks
 
     def local_ks(self, config: NbedConfig, embedded_mol, xc_functional: str, backend=None):
-        """Embedded Kohn-Sham object of ``xc_functional`` (DFT-in-DFT, nbed/driver.py:289-313)."""
+        """Embedded Kohn-Sham object of ``xc_functional`` (DFT-in-DFT, nbed/driver.py:289-313).  As in the reference, this
+        object is NOT wrapped in ``qmmm.mm_charge``: it never sees the MM field."""
         return self._uks(config, embedded_mol, xc_functional, backend)
 
     def local_hf(self, config: NbedConfig, embedded_mol, backend=None, run_qmmm: bool = False):
+        """Embedded HF object (nbed/driver.py:230-260).  With ``run_qmmm`` its core Hamiltonian is hcore + V_mm and its
+        ``energy_nuc()`` returns e_nuc + e_mm, as the ``qmmm.mm_charge`` wrapper of the reference does (:246-253)."""
         from .scf import GpuUHF
 
-        if run_qmmm:
-            raise NbedDriverError("BuiltinHFProvider has no QM/MM point-charge integrals")
         ints = self._integrals(config)
-        return self._adopt(config, GpuUHF(embedded_mol, ints["S"], ints["hcore"], **self._eri_kwargs(config, backend)))
+        hcore, energy_nuc = self._with_mm(config, run_qmmm, backend)
+        local = self._adopt(config, GpuUHF(embedded_mol, ints["S"], hcore, **self._eri_kwargs(config, backend)))
+        if energy_nuc is not None:
+            local.energy_nuc = energy_nuc  # nuclear repulsion + nuclei-MM charges
+        return local
 
 
 class NbedDriver:

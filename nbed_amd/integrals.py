@@ -531,6 +531,117 @@ def two_electron_native(basis: Basis, nthreads: int = 0, cutoff: float = 1e-16) 
     return out
 
 
+def mm_environment(mm_coords, mm_charges, mm_radii, unit: str = "angstrom"):
+    """``NbedConfig``'s three MM fields -> (coords (M, 3) in Bohr, charges (M,), radii (M,) in Bohr).  The reference
+    hands the fields to ``qmmm.mm_charge`` without a ``unit`` (nbed/driver.py:171-180), so coordinates and radii are in
+    the geometry's unit.  ``NbedDriverError`` names the field that has the wrong shape, a non-finite value or a radius
+    that is not positive."""
+    from .exceptions import NbedDriverError
+
+    scale = 1.0 if str(unit).lower().startswith(("b", "au")) else 1.0 / BOHR
+    out = {}
+    m = None  # the number of charges: mm_charges decides it
+    for name, value, tail in (("mm_charges", mm_charges, ()), ("mm_coords", mm_coords, (3,)), ("mm_radii", mm_radii, ())):
+        want = "(M, 3)" if tail else "(M,)"
+        try:
+            arr = np.array(value, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise NbedDriverError(f"{name}: expected numbers of shape {want}") from None
+        if m is None:
+            m = arr.shape[0] if arr.ndim == 1 else None
+        if m is None or arr.shape != (m,) + tail:
+            raise NbedDriverError(f"{name}: shape {arr.shape}, expected {want}" + (f" with M = {m}" if m is not None else ""))
+        if not np.all(np.isfinite(arr)):
+            raise NbedDriverError(f"{name}: every value must be finite")
+        out[name] = arr
+    if not np.all(out["mm_radii"] > 0.0):
+        raise NbedDriverError("mm_radii: every radius must be positive")
+    return np.ascontiguousarray(out["mm_coords"] * scale), out["mm_charges"], out["mm_radii"] * scale
+
+
+def _mm_zetas(radii, m):
+    """1 / zeta = radius^2 per charge; zeros for point charges (``radii`` None)."""
+    return np.zeros(m) if radii is None else np.asarray(radii, dtype=np.float64) ** 2
+
+
+def mm_potential(basis: Basis, coords, charges, radii=None) -> np.ndarray:
+    """V_mm (nao, nao): the potential of MM charges ``charges`` (M,) at ``coords`` (M, 3; Bohr) in the AO basis,
+    V[mu, nu] = - sum_c q_c (mu nu | erf(sqrt(zeta_c) r_C) / r_C) with zeta_c = 1 / radii_c^2 (Gaussian charges; ``radii``
+    None: point charges) -- what PySCF's ``qmmm.mm_charge`` adds to ``get_hcore()``.  Per primitive pair (p, P):
+    - q (2 pi / p) (1 + p / zeta)^(-1/2) sum_tuv E_tuv R_tuv(rho, P - C), rho = p / (1 + p / zeta).  Plain numpy on this
+    module's ``_hermite_r`` / ``_boys``: the slow checker of ``mm_potential_native`` / ``mm_potential_device``."""
+    coords = np.asarray(coords, dtype=np.float64).reshape(-1, 3)
+    charges = np.asarray(charges, dtype=np.float64).reshape(-1)
+    inv_zeta = _mm_zetas(radii, len(charges))
+    n = basis.nao_cart
+    v_mat = np.zeros((n, n))
+    for (ish, sa), (jsh, sb) in itertools.product(enumerate(basis.shells), repeat=2):
+        if not len(charges):
+            break
+        pr = _Pair(sa, sb)
+        pot = None  # Hermite potential of all charges, {(t, u, v): array over the primitive pairs}
+        for pos, q, iz in zip(coords, charges, inv_zeta):
+            s = 1.0 + pr.p * iz
+            d = pr.centre - pos
+            r = _hermite_r(sa.ang + sb.ang, pr.p / s, d[:, 0], d[:, 1], d[:, 2])
+            w = -q / np.sqrt(s)
+            pot = {k: w * val for k, val in r.items()} if pot is None else {k: pot[k] + w * val for k, val in r.items()}
+        for ia, la in enumerate(sa.cart):
+            for ib, lb in enumerate(sb.cart):
+                val = sum(c * pot[k] for k, c in pr.hermite(la, lb).items()) * 2.0 * math.pi / pr.p
+                v_mat[basis.shell_ao0[ish] + ia, basis.shell_ao0[jsh] + ib] = np.dot(pr.weights(ia, ib), val)
+    return basis.to_ao(v_mat)
+
+
+def _mm_arrays(coords, charges, radii):
+    coords = np.ascontiguousarray(np.asarray(coords, dtype=np.float64).reshape(-1, 3))
+    charges = np.ascontiguousarray(np.asarray(charges, dtype=np.float64).reshape(-1))
+    if coords.shape[0] != charges.shape[0]:
+        raise ValueError(f"{coords.shape[0]} positions for {charges.shape[0]} charges")
+    zetas = None
+    if radii is not None:
+        zetas = np.ascontiguousarray(1.0 / np.asarray(radii, dtype=np.float64).reshape(-1) ** 2)
+        if zetas.shape != charges.shape:
+            raise ValueError(f"{zetas.shape[0]} radii for {charges.shape[0]} charges")
+    return coords, charges, zetas
+
+
+def mm_potential_native(basis: Basis, coords, charges, radii=None, nthreads: int = 0) -> np.ndarray:
+    """``mm_potential`` from libnbx's host engine (``nbx_host_mm_potential``, csrc/ints_host.cpp): shell pairs over a
+    thread pool, shells of l <= 3."""
+    import ctypes
+
+    from . import _nbx
+
+    lib = _nbx.load_library()
+    coords, charges, zetas = _mm_arrays(coords, charges, radii)
+    arrays = _shell_arrays(basis)
+    out = np.empty((basis.nao, basis.nao))
+    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    _nbx.check(lib, lib.nbx_host_mm_potential(len(basis.shells), *(ptr(a) for a in arrays), len(charges), ptr(charges),
+                                              ptr(coords), ptr(zetas), int(nthreads), ptr(out)))
+    return out
+
+
+def mm_potential_device(basis: Basis, backend, coords, charges, radii=None, cutoff: float = 1e-16):
+    """``mm_potential`` as a DEVICE matrix (nao, nao) from libnbx's device engine (``nbx_mm_potential``,
+    csrc/mm_potential.hip): lanes over the charges, a workgroup per shell pair and chunk of charges.  Shells of l <= 2."""
+    coords, charges, zetas = _mm_arrays(coords, charges, radii)
+    return backend.mm_potential(basis, coords, charges, zetas, cutoff=cutoff)
+
+
+def mm_nuclear_energy(atoms, coords, charges) -> float:
+    """sum_A sum_c Z_A q_c / |R_A - C_c| (Bohr): what ``qmmm.mm_charge`` adds to ``energy_nuc()``.  Plain point charges,
+    with or without radii."""
+    coords = np.asarray(coords, dtype=np.float64).reshape(-1, 3)
+    charges = np.asarray(charges, dtype=np.float64).reshape(-1)
+    e = 0.0
+    for sym, pos in atoms:
+        if len(charges):
+            e += NUCLEAR_CHARGE[sym] * float(np.sum(charges / np.linalg.norm(coords - pos, axis=1)))
+    return e
+
+
 def max_ang(basis: Basis) -> int:
     """Highest angular momentum of a shell of the basis (the device engine covers l <= 2)."""
     return max(int(s.ang) for s in basis.shells)
