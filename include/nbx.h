@@ -936,6 +936,26 @@ int nbx_ccsd_tau(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_t1, c
  * device double d_maxerr.  d_t_new and d_err are typically a slot of the DIIS history.              */
 int nbx_ccsd_update(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_r, const double* d_t_old,
                     const double* d_eo, const double* d_ev, double* d_t_new, double* d_err, double* d_maxerr);
+/* Perturbative triples (csrc/ccsd_t.hip): the (T) a PySCF user adds with ccsd_t() to the CCSD of
+ * nbed/driver.py:1105-1135, in the non-HF form (f_ov != 0) over semicanonical spin orbitals (f_oo, f_vv
+ * diagonal: d_eo, d_ev).  d_cubes holds ncubes <= 65535 cubes W (nvir, nvir, nvir), cube x that of the
+ * occupied triple i < j < k = d_ijk[3x .. 3x+2] (device ints, trusted), built by the caller with nbx_gemm:
+ *      W[a,b,c] = P(i/jk) [ sum_e t2[j,k,a,e] <ei||bc> - sum_m t2[i,m,b,c] <ma||jk> ],
+ *      P(p/qr) g(pqr) = g(pqr) - g(qpr) - g(rqp).
+ * For every a < b < c the kernel forms w = W[a,b,c] - W[b,a,c] - W[c,b,a], the disconnected part
+ *      t_d = P(i/jk) P(a/bc) [ t1[i,a] oovv[j,k,b,c] + fov[i,a] t2[j,k,b,c] ],
+ * D = eo[i] + eo[j] + eo[k] - ev[a] - ev[b] - ev[c], and writes  sum_x sum_{a<b<c} w (w + t_d) / D  into the
+ * device double d_energy.  The cube is tiled 16 (a) x 4 (b) x 16 (c) through LDS so that all three reads run
+ * along the fastest index; nbx_ccsd_triples_tile() returns the 16.  No atomics: every workgroup writes its
+ * partial sum into d_work (nbx_ccsd_triples_worksize bytes, every slot written) and one workgroup adds them in
+ * a fixed order, so equal (nocc, nvir, ncubes) and inputs give equal bits.  nocc < 3, nvir < 3 or ncubes == 0:
+ * d_energy = 0, nothing else launched.  NBX_E_NOMEM for a short workspace.  Does not synchronise.        */
+size_t nbx_ccsd_triples_worksize(int64_t nvir, int64_t ncubes);
+int nbx_ccsd_triples_tile(void);
+int nbx_ccsd_triples_energy(nbx_ctx* ctx, int64_t nocc, int64_t nvir, int64_t ncubes, const double* d_cubes,
+                            const int* d_ijk, const double* d_t1, const double* d_fov, const double* d_t2,
+                            const double* d_oovv, const double* d_eo, const double* d_ev, void* d_work,
+                            size_t work_bytes, double* d_energy);
 
 /* ------------------------------------------------------------------ full CI (csrc/fci.hip)
  * What surrounds the GEMM of a determinant FCI sigma build (nbed_amd/fci_gpu.py): the reference runs PySCF's

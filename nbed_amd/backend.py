@@ -1714,8 +1714,29 @@ class HipBackend:
     def free_bytes(self) -> int:
         return int(self.torch.cuda.mem_get_info(self.device_index)[0])
 
+    def ccsd_triples_tile(self) -> int:
+        """Edge (along a and c) of the cube tile of ``nbx_ccsd_triples_energy``."""
+        return int(self.lib.nbx_ccsd_triples_tile())
+
+    def ccsd_triples_work_doubles(self, nv: int, ncubes: int) -> int:
+        """Doubles of partial sums ``ccsd_triples_energy`` needs for ``ncubes`` cubes of ``nv`` virtuals."""
+        return int(self.lib.nbx_ccsd_triples_worksize(nv, ncubes)) // 8
+
+    def ccsd_triples_energy(self, no: int, nv: int, cubes, ijk, t1, fov, t2, oovv, eo, ev, work, out):
+        """sum over the cubes (ncubes, nv, nv, nv) of the occupied triples ``ijk`` (device int32, (ncubes, 3), i < j < k)
+        and over a < b < c of w (w + t_d) / D into the device double ``out`` (include/nbx.h, "coupled cluster", (T))."""
+        ncubes = int(ijk.numel()) // 3
+        if ijk.dtype != self.torch.int32 or cubes.numel() < ncubes * nv**3:
+            raise ValueError("ccsd_triples_energy: ijk must be int32 and cubes hold one (nv, nv, nv) cube per triple")
+        if t1.numel() != no * nv or fov.numel() != no * nv or t2.numel() != (no * nv) ** 2 or oovv.numel() != t2.numel() \
+                or eo.numel() != no or ev.numel() != nv:
+            raise ValueError("ccsd_triples_energy: operand shapes")
+        self._call("nbx_ccsd_triples_energy", no, nv, ncubes, self._p(cubes), self._p(ijk), self._p(t1), self._p(fov),
+                   self._p(t2), self._p(oovv), self._p(eo), self._p(ev), self._p(work), 8 * work.numel(), self._p(out))
+
     def ccsd(self, spatial, occupied, **kwargs):
-        """Spin-orbital CCSD on the device (``nbed_amd.ccsd_gpu.solve_spatial``): the capability the driver asks for."""
+        """Spin-orbital CCSD on the device (``nbed_amd.ccsd_gpu.solve_spatial``): the capability the driver asks for;
+        ``triples=True`` adds the (T) energy as ``e_t``."""
         from . import ccsd_gpu
 
         return ccsd_gpu.solve_spatial(spatial, occupied, backend=self, **kwargs)

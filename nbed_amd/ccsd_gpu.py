@@ -12,7 +12,10 @@ dense numpy einsum on the host, for up to 40 spin orbitals.  This module is that
   i < j, a < b, e < f, and W_abef is never formed: its t1 <ov||vv> pieces go through an o^3 v intermediate and its
   1/4 tau <oo||vv> piece through W_mnij;
 * MP2 start, amplitude DIIS (space 6, from the second stored vector) and the convergence rule are those of
-  ``ccsd.solve``, so the iterates follow the host solver's and can be compared cycle by cycle.
+  ``ccsd.solve``, so the iterates follow the host solver's and can be compared cycle by cycle;
+* ``triples=True``: after the loop the (T) energy of ``ccsd.triples_correction`` from the device-resident amplitudes and
+  blocks (``triples_from_blocks``): semicanonical rotation, one v x v^2 cube per occupied triple from six ``nbx_gemm``
+  calls, antisymmetriser, denominators and energy sum in ``nbx_ccsd_triples_energy`` (csrc/ccsd_t.hip).
 
 ``torch`` only allocates and views; per cycle three groups of scalars reach the host (energy, max |err|, DIIS dots).
 """
@@ -68,6 +71,49 @@ def memory_plan(no: int, nv: int, diis_space: int = 6) -> dict:
     }
     plan["total"] = sum(plan.values())
     return plan
+
+
+TRIPLES_TILE = (16, 4, 16)  # cube tile (a, b, c) of nbx_ccsd_triples_energy (csrc/ccsd_t.hip)
+
+
+def _ntriple(n: int) -> int:
+    return n * (n - 1) * (n - 2) // 6
+
+
+def triples_memory_plan(no: int, nv: int, batch: int) -> dict:
+    """Bytes the (T) step needs on top of the blocks and amplitudes the CCSD loop leaves on the device, by group (host
+    arithmetic; ``memory_plan`` is the loop's own and does not know about it):
+
+    rotated    the semicanonical t1, f_ov, t2, <oo||vv>, <ov||vv>, <ov||oo>, the (j, k, m, a) copy of the last one the
+               hole term reads, and the list of triples
+    work       the rotation of <ov||vv>, the largest: its input is one of the loop's blocks, so two intermediates of
+               its size and the result of a permuted product on top of what ``rotated`` already counts
+    cubes      ``batch`` cubes of nv^3 doubles
+    partials   one double per workgroup of the energy kernel and per cube, and the per-batch energies
+    """
+    if batch < 1:
+        raise ValueError("triples_batch must be at least 1")
+    ta, tb, tc = TRIPLES_TILE
+    tiles = -(-nv // ta) * -(-nv // tb) * -(-nv // tc)
+    ntri = _ntriple(no)
+    plan = {
+        "rotated": 8 * (2 * no * nv + 2 * (no * nv) ** 2 + no * nv**3 + 2 * no**3 * nv) + 4 * 3 * ntri,
+        "work": 8 * 3 * no * nv**3,
+        "cubes": 8 * batch * nv**3,
+        "partials": 8 * (batch * tiles + max(ntri, 1)),  # (a slot per triple: room for any batch, so linear in it)
+    }
+    plan["total"] = sum(plan.values())
+    return plan
+
+
+def default_triples_batch(no: int, nv: int, free: int) -> int:
+    """Cubes in flight when the caller names none: as many as fit into half of the ``free`` bytes the fixed groups of
+    ``triples_memory_plan`` leave, at most 64 (past that a batch is GEMM work for every CU many times over) and at most
+    the number of triples; at least 1 -- whether one fits is for the caller to check."""
+    one, two = triples_memory_plan(no, nv, 1), triples_memory_plan(no, nv, 2)
+    per_cube = two["total"] - one["total"]
+    room = (free - (one["total"] - per_cube)) // 2
+    return int(max(1, min(64, _ntriple(no), room // max(per_cube, 1))))
 
 
 class Contractor:
@@ -161,12 +207,12 @@ def spatial_from_dense(h1: np.ndarray, h2: np.ndarray):
 
 
 def solve(constant, h1, h2, occupied, conv_tol: float = 1e-10, max_cycle: int = 200, diis_space: int = 6,
-          backend=None) -> CCSDResult:
+          backend=None, triples: bool = False, triples_batch: int | None = None) -> CCSDResult:
     """``ccsd.solve`` on the device, from the dense spin-orbital tensors of ``build()`` (direct use and tests; the driver
     calls ``solve_spatial``, which never holds a (2n)^4 tensor)."""
     one, two = spatial_from_dense(h1, h2)
     return solve_spatial((constant, one, two), occupied, conv_tol=conv_tol, max_cycle=max_cycle, diis_space=diis_space,
-                         backend=backend)
+                         backend=backend, triples=triples, triples_batch=triples_batch)
 
 
 def _device_backend(backend):
@@ -179,13 +225,112 @@ def _device_backend(backend):
     return backend
 
 
+def _rotate4(c, x, us):
+    """x[w,x,y,z] -> sum x[a,b,c,d] u0[a,w] u1[b,x] u2[c,y] u3[d,z], one axis per product."""
+    x = c("ap,abcd->pbcd", us[0], x)
+    x = c("abcd,bq->aqcd", x, us[1])
+    x = c("abcd,cr->abrd", x, us[2])
+    return c("abcd,ds->abcs", x, us[3])
+
+
+def triples_from_blocks(t1, t2, fov, foo, fvv, oovv, ovvv, ovoo, occ_spins, vir_spins, batch: int | None = None,
+                        backend=None, stats: dict | None = None) -> float:
+    """The (T) energy of ``ccsd.triples_correction`` on the device, from the amplitudes, the Fock blocks and the three
+    Hamiltonian blocks it reads (device tensors as the CCSD loop leaves them, or host arrays) in any orbital basis whose
+    spin orbitals have the spins ``occ_spins`` / ``vir_spins`` (0 alpha, 1 beta).
+
+    f_oo and f_vv are diagonalised on the host, one eigenproblem per spin (``ccsd.spin_block_eigh``: alpha never mixes
+    with beta); the operands are always rotated, on the device, through ``Contractor``.  For every occupied triple
+    i < j < k six batched ``nbx_gemm`` calls accumulate the cube W[a,(bc)] -- particle and hole term of (i|jk), (j|ik),
+    (k|ji) -- and ``nbx_ccsd_triples_energy`` reduces ``batch`` cubes at a time.  The per-batch energies are added on the
+    host in batch order, so one (o, v, batch) always gives the same bits."""
+    from .ccsd import spin_block_eigh
+
+    be = _device_backend(backend)
+    foo_h, fvv_h = np.asarray(be.to_host(foo), dtype=float), np.asarray(be.to_host(fvv), dtype=float)
+    no, nv = int(foo_h.shape[0]), int(fvv_h.shape[0])
+    if stats is not None:
+        stats.update(triples=_ntriple(no), triples_batch=0, triples_seconds=0.0)
+    if no < 3 or nv < 3:
+        return 0.0  # no triple excitation: nothing is launched
+    ntri = _ntriple(no)
+    free = be.free_bytes()
+    plan = triples_memory_plan(no, nv, 1)
+    if plan["total"] > free:
+        raise NbedDriverError(
+            f"the (T) step of {no} occupied and {nv} virtual spin orbitals needs {plan['total']} bytes of device memory "
+            f"with one cube in flight ({plan['rotated']} for the semicanonical operands, {plan['work']} to rotate them, "
+            f"{plan['cubes']} per cube, {plan['partials']} of partial sums); {free} are free")
+    if batch is None:
+        batch = default_triples_batch(no, nv, free)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("triples_batch must be at least 1")
+    batch = min(batch, ntri, 65535)
+    plan = triples_memory_plan(no, nv, batch)
+    if plan["total"] > free:
+        raise NbedDriverError(f"the (T) step with {batch} cubes in flight needs {plan['total']} bytes of device memory "
+                              f"({plan['cubes']} for the cubes); {free} are free")
+    t_start = time.perf_counter()
+    c = Contractor(be)
+    eo_h, uo_h = spin_block_eigh(foo_h, occ_spins)
+    ev_h, uv_h = spin_block_eigh(fvv_h, vir_spins)
+    eo, ev, uo, uv = be.asarray(eo_h), be.asarray(ev_h), be.asarray(uo_h), be.asarray(uv_h)
+    t1s = c("pa,aq->pq", c("ip,ia->pa", uo, be.asarray(t1)), uv)
+    fovs = c("pa,aq->pq", c("ip,ia->pa", uo, be.asarray(fov)), uv)
+    t2s = _rotate4(c, be.asarray(t2), (uo, uo, uv, uv))
+    oovvs = _rotate4(c, be.asarray(oovv), (uo, uo, uv, uv))
+    ovvvs = _rotate4(c, be.asarray(ovvv), (uo, uv, uv, uv))
+    ovoo_jkma = be.permute4(_rotate4(c, be.asarray(ovoo), (uo, uv, uo, uo)), [2, 3, 0, 1])
+    triples = [(i, j, k) for i in range(no) for j in range(i + 1, no) for k in range(j + 1, no)]
+    ijk = be.int_array(np.array(triples, dtype=np.int32).reshape(-1, 3))
+    v2, v3, ov = nv * nv, nv**3, no * nv
+    cubes = be.empty((batch, nv, v2))
+    work = be.empty(max(be.ccsd_triples_work_doubles(nv, batch), 1))
+    nbatch = -(-ntri // batch)
+    energies = be.empty(nbatch)
+    t2f, ovvvf, ovoof, cubesf = t2s.view(-1), ovvvs.view(-1), ovoo_jkma.view(-1), cubes.view(-1)
+
+    def product(trans_a, kk, alpha, a, a_off, sa, b, b_off, sb, beta, slot, count):
+        be.gemm_raw(trans_a, "N", nv, v2, kk, alpha, a[a_off:], nv, sa, b[b_off:], v2, sb, beta, cubesf[slot * v3:], v2, v3,
+                    count)
+
+    for x in range(nbatch):
+        t0 = x * batch
+        nb = min(batch, ntri - t0)
+        s = 0
+        while s < nb:  # runs of triples that share (i, j): k = k0, k0 + 1, ... ride on the GEMM's batch strides
+            i, j, k0 = triples[t0 + s]
+            n = min(no - k0, nb - s)
+            # (i|jk): - sum_e t2[j,k,a,e] ovvv[i,e,(bc)] - sum_m ovoo[m,a,j,k] t2[i,m,(bc)]   (beta = 0: writes the cube)
+            product("N", nv, -1.0, t2f, (j * no + k0) * v2, v2, ovvvf, i * v3, 0, 0.0, s, n)
+            product("T", no, -1.0, ovoof, (j * no + k0) * ov, ov, t2f, i * no * v2, 0, 1.0, s, n)
+            # -(j|ik)
+            product("N", nv, 1.0, t2f, (i * no + k0) * v2, v2, ovvvf, j * v3, 0, 1.0, s, n)
+            product("T", no, 1.0, ovoof, (i * no + k0) * ov, ov, t2f, j * no * v2, 0, 1.0, s, n)
+            # -(k|ji)
+            product("N", nv, 1.0, t2f, (j * no + i) * v2, 0, ovvvf, k0 * v3, v3, 1.0, s, n)
+            product("T", no, 1.0, ovoof, (j * no + i) * ov, 0, t2f, k0 * no * v2, no * v2, 1.0, s, n)
+            s += n
+        be.ccsd_triples_energy(no, nv, cubes, ijk[t0:t0 + nb].reshape(-1), t1s, fovs, t2s, oovvs, eo, ev, work,
+                               energies[x:x + 1])
+    e_t = 0.0
+    for part in be.to_host(energies):
+        e_t += float(part)
+    if stats is not None:
+        stats.update(triples_batch=batch, triples_plan=plan, triples_seconds=time.perf_counter() - t_start)
+    return e_t
+
+
 def solve_spatial(spatial, occupied, conv_tol: float = 1e-10, max_cycle: int = 200, diis_space: int = 6, backend=None,
-                  stats: dict | None = None) -> CCSDResult:
+                  stats: dict | None = None, triples: bool = False, triples_batch: int | None = None) -> CCSDResult:
     """CCSD of the determinant that occupies the spin orbitals ``occupied`` (index 2p + s, alpha even).
 
     ``spatial``: a ``SpatialHamiltonian``, or ``(constant, one_body (2,n,n), two_body (3,n,n,n,n))`` with the blocks of
     ``build_spatial()`` (thresholded, the two-body ones halved) as host or device arrays.  ``stats``, if given, receives
-    the bytes planned and the seconds per cycle."""
+    the bytes planned and the seconds per cycle.  ``triples``: after the loop, the (T) energy of
+    ``triples_from_blocks`` from the device-resident amplitudes and blocks, as ``e_t`` of the result; ``triples_batch``:
+    its cubes in flight (default: what ``default_triples_batch`` fits into the free memory)."""
     be = _device_backend(backend)
     if hasattr(spatial, "two_body"):
         constant, one, two = spatial.constant, spatial.one_body, spatial.two_body
@@ -368,4 +513,13 @@ def solve_spatial(spatial, occupied, conv_tol: float = 1e-10, max_cycle: int = 2
             break
     if stats is not None:
         stats.update(cycle_seconds=cycle_seconds, iterations=it)
-    return CCSDResult(e_hf, e_old, be.to_host(t1).copy(), be.to_host(t2).copy(), converged, it)
+    t1_h, t2_h = be.to_host(t1).copy(), be.to_host(t2).copy()
+    e_t = None
+    if triples:
+        # (T) from what is on the device now, after the loop's own memory is handed back: the DIIS history, the packed
+        # <vv||vv>, the residual and the blocks (T) does not read
+        del hist_t, hist_e, vvvv_p, res, r1, r2, tau, oooo, ovvo, ovov, ooov, vvvo, g
+        be.torch.cuda.empty_cache()
+        e_t = triples_from_blocks(t1, t2, fov, foo_h, fvv_h, oovv, ovvv, ovoo, [p & 1 for p in occ], [p & 1 for p in vir],
+                                  batch=triples_batch, backend=be, stats=stats)
+    return CCSDResult(e_hf, e_old, t1_h, t2_h, converged, it, e_t)

@@ -509,12 +509,16 @@ class BuiltinHFProvider:
 class NbedDriver:
     """Run projection-based embedding and produce the embedded active-space Hamiltonian."""
 
-    def __init__(self, config: NbedConfig, provider=None, backend=None, hamiltonian_format: str = "dense"):
+    def __init__(self, config: NbedConfig, provider=None, backend=None, hamiltonian_format: str = "dense",
+                 ccsd_triples: bool | None = None):
         """``hamiltonian_format``: "dense" -- ``result["second_quantised"]`` is the reference's
         ``(constant, h1 (2n,2n), h2 (2n,2n,2n,2n))``; "spatial" -- a ``SpatialHamiltonian`` (three unique
-        spin blocks, 16/3 times smaller; ``.to_dense()`` gives the former)."""
+        spin blocks, 16/3 times smaller; ``.to_dense()`` gives the former).  ``ccsd_triples``: the embedded CCSD also
+        reports CCSD(T) (``result["e_ccsd_t"]``, ``result["ccsd_t_emb"]``); ``None`` reads ``NBED_CCSD_TRIPLES`` = 0
+        (default) | 1."""
         if hamiltonian_format not in ("dense", "spatial"):
             raise NbedDriverError(f"unknown hamiltonian_format {hamiltonian_format!r}")
+        self.ccsd_triples = ccsd_triples
         self.hamiltonian_format = hamiltonian_format
         self.config = config
         self._provider = provider
@@ -575,12 +579,18 @@ class NbedDriver:
         """CCSD of an SCF object: PySCF's solver where there is one, else the spin-orbital equations over the
         Hamiltonian ``HamiltonianBuilder`` makes of it -- on the host for small orbital spaces (``nbed_amd.ccsd``), on
         the device above its cap when the backend offers ``ccsd`` (``nbed_amd.ccsd_gpu``).  ``NBED_CCSD_SOLVER`` =
-        ``auto`` (default) | ``host`` | ``device`` forces either of the two at any size it accepts."""
+        ``auto`` (default) | ``host`` | ``device`` forces either of the two at any size it accepts.  With the triples
+        switched on (``ccsd_triples`` / ``NBED_CCSD_TRIPLES=1``) whichever solver runs also leaves the (T) energy in
+        ``e_t``."""
         mode = os.environ.get("NBED_CCSD_SOLVER", "auto")
         if mode not in ("auto", "host", "device"):
             raise NbedDriverError(f"NBED_CCSD_SOLVER={mode!r}: expected 'auto', 'host' or 'device'")
+        triples = self._want_triples()
         try:
-            return run_emb_ccsd(scf_obj, frozen, self.config.convergence, self.config.max_ram_memory)[0]
+            cc = run_emb_ccsd(scf_obj, frozen, self.config.convergence, self.config.max_ram_memory)[0]
+            if triples:
+                cc.e_t = float(cc.ccsd_t())  # PySCF's own (T) on its own amplitudes
+            return cc
         except NbedDriverError:
             from . import ccsd
 
@@ -603,9 +613,22 @@ class NbedDriver:
                                       f"orbitals, the molecule {na} + {nb} electrons")
             conv_tol = min(self.config.convergence, 1e-8)
             if on_device:  # the three spatial spin blocks stay on the device; no (2n)^4 tensor anywhere
+                if triples:
+                    return self.be.ccsd(builder.build_spatial_device(), occupied, conv_tol=conv_tol, triples=True)
                 return self.be.ccsd(builder.build_spatial_device(), occupied, conv_tol=conv_tol)
             const, h1, h2 = builder.build()
+            if triples:
+                return ccsd.solve(const, h1, h2, occupied, conv_tol=conv_tol, triples=True)
             return ccsd.solve(const, h1, h2, occupied, conv_tol=conv_tol)
+
+    def _want_triples(self) -> bool:
+        """The ``ccsd_triples`` argument, or ``NBED_CCSD_TRIPLES`` = 0 (default) | 1 where it is ``None``."""
+        if self.ccsd_triples is not None:
+            return bool(self.ccsd_triples)
+        flag = os.environ.get("NBED_CCSD_TRIPLES", "0")
+        if flag not in ("0", "1"):
+            raise NbedDriverError(f"NBED_CCSD_TRIPLES={flag!r}: expected '0' or '1'")
+        return flag == "1"
 
     @cached_property
     def _global_ccsd(self):
@@ -959,6 +982,9 @@ class NbedDriver:
             ccsd_emb, _ = self._run_emb_ccsd(result["scf"])
             result["e_ccsd"] = ccsd_emb.e_tot + self.e_env + self.two_e_cross - corr
             result["ccsd_emb"] = ccsd_emb.e_tot - self.e_nuc
+            if self._want_triples():
+                result["e_ccsd_t"] = result["e_ccsd"] + ccsd_emb.e_t
+                result["ccsd_t_emb"] = result["ccsd_emb"] + ccsd_emb.e_t
         if cfg.run_fci_emb is True:
             fci_emb = self._run_emb_fci(result["scf"])
             result["e_fci"] = fci_emb.e_tot + self.e_env + self.two_e_cross - corr

@@ -11,10 +11,11 @@ from .driver import NbedDriver
 
 
 def nbed(config: NbedConfig | str | Path | None = None, provider=None, backend=None,
-         hamiltonian_format: str = "dense", **config_kwargs) -> NbedDriver:
-    """Validate the configuration, run ``NbedDriver.embed()`` and return the driver."""
+         hamiltonian_format: str = "dense", ccsd_triples: bool | None = None, **config_kwargs) -> NbedDriver:
+    """Validate the configuration, run ``NbedDriver.embed()`` and return the driver (``ccsd_triples``: as
+    ``NbedDriver``'s, not a configuration field)."""
     driver = NbedDriver(parse_config(config, **config_kwargs), provider=provider, backend=backend,
-                        hamiltonian_format=hamiltonian_format)
+                        hamiltonian_format=hamiltonian_format, ccsd_triples=ccsd_triples)
     driver.embed()
     return driver
 

@@ -2,7 +2,9 @@
 Default: octane / 6-31G*, 4 active atoms, SPADE + concentric localisation, Huzinaga projector, HF-in-HF -- about 128
 embedded MOs, 256 spin orbitals, far past the 40 of the host solver.
 
-    python tools/time_ccsd.py [octane|water] [basis] [n_active_atoms] [max_cycle]"""
+    python tools/time_ccsd.py [octane|water] [basis] [n_active_atoms] [max_cycle] [--triples]
+
+``--triples``: the (T) step after the loop (from whatever amplitudes ``max_cycle`` left), its seconds against the cycle's."""
 import sys
 import time
 
@@ -17,10 +19,12 @@ from nbed_amd.backend import HipBackend  # noqa: E402
 from nbed_amd.driver import BuiltinHFProvider  # noqa: E402
 from nbed_amd.ham_builder import HamiltonianBuilder  # noqa: E402
 
-name = sys.argv[1] if len(sys.argv) > 1 else "octane"
-basis = sys.argv[2] if len(sys.argv) > 2 else "6-31g*"
-nact = int(sys.argv[3]) if len(sys.argv) > 3 else 4
-max_cycle = int(sys.argv[4]) if len(sys.argv) > 4 else 200
+triples = "--triples" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--triples"]
+name = args[0] if len(args) > 0 else "octane"
+basis = args[1] if len(args) > 1 else "6-31g*"
+nact = int(args[2]) if len(args) > 2 else 4
+max_cycle = int(args[3]) if len(args) > 3 else 200
 geom = octane_xyz() if name == "octane" else "3\n\nO 0 0 0.115\nH 0 0.754 -0.459\nH 0 -0.754 -0.459"
 
 be = HipBackend()
@@ -43,9 +47,9 @@ t2 = time.perf_counter()
 print(f"spatial Hamiltonian blocks on the device: {t2 - t1:.2f} s", flush=True)
 torch.cuda.reset_peak_memory_stats()
 stats = {}
-cc = ccsd_gpu.solve_spatial(spatial, occupied, conv_tol=1e-8, max_cycle=max_cycle, backend=be, stats=stats)
+cc = ccsd_gpu.solve_spatial(spatial, occupied, conv_tol=1e-8, max_cycle=max_cycle, backend=be, stats=stats, triples=triples)
 torch.cuda.synchronize()
-t3 = time.perf_counter()
+t3 = time.perf_counter() - stats.get("triples_seconds", 0.0)
 cyc = np.array(stats["cycle_seconds"])
 plan = stats["plan"]
 print(f"CCSD: {stats['nocc']} occupied + {stats['nvir']} virtual spin orbitals, {cc.iterations} cycles, converged={cc.converged}, "
@@ -54,3 +58,8 @@ print(f"total {t3 - t2:.2f} s (blocks + MP2 start {t3 - t2 - cyc.sum():.2f} s); 
       f"first {cyc[0] * 1e3:.1f} ms, min {cyc.min() * 1e3:.1f} ms")
 print("bytes planned: " + ", ".join(f"{k} {v / 1e9:.2f} GB" for k, v in plan.items())
       + f"; peak allocated by torch {torch.cuda.max_memory_allocated() / 1e9:.2f} GB")
+if triples:
+    tplan = stats["triples_plan"]
+    print(f"(T): E_T = {cc.e_t:.10f}, {stats['triples']} triples, {stats['triples_batch']} cubes in flight, "
+          f"{stats['triples_seconds']:.2f} s = {stats['triples_seconds'] / np.median(cyc):.1f} CCSD cycles")
+    print("(T) bytes planned: " + ", ".join(f"{k} {v / 1e9:.2f} GB" for k, v in tplan.items()))
