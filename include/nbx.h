@@ -358,6 +358,35 @@ int nbx_transpose(nbx_ctx* ctx, int64_t rows, int64_t cols, int64_t batch, const
 /* A[:, j] *= s[j]  (columns scaled; row-major (rows x cols)). */
 int nbx_scale_cols(nbx_ctx* ctx, int64_t rows, int64_t cols, int64_t batch, const double* d_s,
                    double* d_a);
+/* Test support, like nbx_gemm_route: which kernel instance the launch functions above pick -- the functions they
+ * call themselves, host arithmetic only (no context, no GPU), and the only statement of these limits.
+ * tests/scf_kernel_cases.py keeps shapes per instance and tests/test_host_scf_kernel_cases.py fails when a retuned
+ * threshold moves one of them.
+ * nbx_cycle_scalars_route: the energy / |dD| scalars of a cycle.  nocc_a = nocc_b = -1: of given matrices
+ * (nbx_huz_cycle_scalars_dev / _dts and the mu-shift cycle: 16 x 16 tiles while their partial sums fit the context's
+ * scratch, 32 x 32 tiles while those fit, refused beyond).  nocc_a, nocc_b >= 0: inside nbx_huz_cycle -- T16_DENS
+ * where the kernel also makes the aufbau density (16 x 16 tiles, both spins occupied and no wider than the kernel's
+ * operand registers), else what the density product + the form above run on.  The limits themselves are stated in
+ * csrc/elementwise.hip (scalars_route, density_scalars_fused) and nowhere else: ask this function.
+ * (The synchronous nbx_huz_cycle_scalars always runs on 32 x 32 tiles and is refused where T32 would be.)          */
+#define NBX_CYCLE_SCALARS_REFUSED 0
+#define NBX_CYCLE_SCALARS_T32 1      /* huz_scalars_kernel<32> */
+#define NBX_CYCLE_SCALARS_T16 2      /* huz_scalars_kernel<16> */
+#define NBX_CYCLE_SCALARS_T16_DENS 3 /* huz_scalars_kernel<16, true>: density and scalars in one launch */
+int nbx_cycle_scalars_route(int64_t nao, int64_t nocc_a, int64_t nocc_b);
+/* nbx_diis_update / _err on vectors of n doubles with nd vectors held: the Pulay solve and the extrapolation in one
+ * kernel while the Pulay matrix fits one element per lane, or the general solver followed by the linear combination
+ * (diis_route in csrc/elementwise.hip).                                                                          */
+#define NBX_DIIS_REFUSED 0
+#define NBX_DIIS_FUSED 1   /* diis_solve8_lincomb_kernel */
+#define NBX_DIIS_GENERAL 2 /* diis_solve_kernel + lincomb_dev_kernel */
+int nbx_diis_route(int64_t n, int64_t nd);
+/* nbx_vo_sumsq: one workgroup per spin that stores its sum (small virtual-occupied blocks), or 32 per spin and a
+ * second stage (vo_sumsq_route in csrc/elementwise.hip).                                                          */
+#define NBX_VO_SUMSQ_REFUSED 0
+#define NBX_VO_SUMSQ_ONE_WG 1
+#define NBX_VO_SUMSQ_32_WG 2
+int nbx_vo_sumsq_route(int64_t nao, int64_t nocc_a, int64_t nocc_b);
 
 /* ------------------------------------------------------------------ symmetric eigensolver
  * Replaces np.linalg.eigh (LAPACK dsyevd) at nbed/scf/huzinaga_scf.py:145,168 and the

@@ -35,6 +35,10 @@ ERI_CLASSES = 25  # (la + lb, lc + ld), index 5 l_ab + l_cd
 GEMM_KERNEL_NONE, GEMM_KERNEL_SMALL, GEMM_KERNEL_T32, GEMM_KERNEL_T64, GEMM_KERNEL_T128, GEMM_KERNEL_TN_DMA = range(6)
 # nbx_jk_packed_route answers (NBX_JK_KERNEL_*)
 JK_KERNEL_NONE, JK_KERNEL_S4, JK_KERNEL_M4, JK_KERNEL_M8, JK_KERNEL_MX, JK_KERNEL_MX_HI = range(6)
+# nbx_cycle_scalars_route / nbx_diis_route / nbx_vo_sumsq_route answers (NBX_CYCLE_SCALARS_*, NBX_DIIS_*, NBX_VO_SUMSQ_*)
+CYCLE_SCALARS_REFUSED, CYCLE_SCALARS_T32, CYCLE_SCALARS_T16, CYCLE_SCALARS_T16_DENS = range(4)
+DIIS_REFUSED, DIIS_FUSED, DIIS_GENERAL = range(3)
+VO_SUMSQ_REFUSED, VO_SUMSQ_ONE_WG, VO_SUMSQ_32_WG = range(3)
 
 
 class NbxError(RuntimeError):
@@ -129,6 +133,9 @@ SIGNATURES = {
     "nbx_dots": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, POINTER(c_double)]),
     "nbx_transpose": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
     "nbx_scale_cols": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
+    "nbx_cycle_scalars_route": (c_int, [c_int64, c_int64, c_int64]),
+    "nbx_diis_route": (c_int, [c_int64, c_int64]),
+    "nbx_vo_sumsq_route": (c_int, [c_int64, c_int64, c_int64]),
     "nbx_eigh_worksize": (c_size_t, [c_int64, c_int64]),
     "nbx_eigh": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, c_size_t]),
     "nbx_eigh_warm": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, c_size_t]),

@@ -10,6 +10,7 @@
 namespace {
 
 constexpr int TILE = 32;
+constexpr int DENS_MAX_NOCC = 64;  // huz_scalars_kernel<16, true> holds the operands of this many k: 16 MFMA steps of four
 
 // ---------------------------------------------------------------- reductions
 // Stage 2 of every scalar reduction: out[o] = sum_b partial[b * nout + o] (fixed order).
@@ -249,7 +250,7 @@ __global__ void huz_scalars_kernel(const double* __restrict__ h, int h3d, const 
     // -- which saves that build its preparation launch.  Tiles on or below the diagonal write.
     double dsum[R], tsum[R];
     double ham[2][R], dv[2][R], dold[2][R];
-    constexpr int DSTEPS = 16;  // MFMA steps of four k: nocc <= 64 (the caller checks)
+    constexpr int DSTEPS = DENS_MAX_NOCC / 4;  // MFMA steps of four k (the caller checks nocc)
     double ca[DENS ? DSTEPS : 1], cb[DENS ? DSTEPS : 1];
     if (DENS) {
         // wavefront x: operands of the whole k range of spin x requested in one trip (A: row i0 + fr, B: row j0 + fr of C)
@@ -894,8 +895,9 @@ __device__ __forceinline__ void diis_jacobi8(double& a, double& v, int m, double
 
 // One wavefront per workgroup; EVERY workgroup solves the same system with the same instructions (the answer is
 // the same bits everywhere) and then extrapolates its share of the vector: the solve costs no launch of its own.
-// Workgroup 0 also stores the new row / column of H and the coefficients.  nd <= 7.
+// Workgroup 0 also stores the new row / column of H and the coefficients.  nd <= DIIS8_MAX_ND.
 constexpr int DIIS8_PER_LANE = 4;  // vector elements per lane
+constexpr int DIIS8_MAX_ND = 7;    // a Pulay matrix of order nd + 1 <= 8, one element per lane (diis_route below decides)
 __global__ __launch_bounds__(64) void diis_solve8_lincomb_kernel(const double* __restrict__ partial, int nblocks,
                                                                  int nd, int slot, double* __restrict__ H, int ldh,
                                                                  double* __restrict__ coef,
@@ -912,11 +914,11 @@ __global__ __launch_bounds__(64) void diis_solve8_lincomb_kernel(const double* _
     const bool inside = r < m && c < m;
     const bool new_row = inside && r == slot + 1 && c >= 1, new_col = inside && c == slot + 1 && r >= 1;
     const double hold = (inside && !new_row && !new_col) ? H[(int64_t)r * ldh + c] : 0.0;
-    double xv[DIIS8_PER_LANE][7];  // (in flight during the solve; 1e300 would show a use of an unloaded one)
+    double xv[DIIS8_PER_LANE][DIIS8_MAX_ND];  // (in flight during the solve; 1e300 would show a use of an unloaded one)
 #pragma unroll
     for (int j = 0; j < DIIS8_PER_LANE; ++j)
 #pragma unroll
-        for (int k = 0; k < 7; ++k) xv[j][k] = (k < nd && i0 + 64 * j < n) ? vecs[k * stride + i0 + 64 * j] : 0.0;
+        for (int k = 0; k < DIIS8_MAX_ND; ++k) xv[j][k] = (k < nd && i0 + 64 * j < n) ? vecs[k * stride + i0 + 64 * j] : 0.0;
     const double v_prev = state[lane];
     // (a basis of a LARGER system would mix the zero padding into the live indices: cold start then)
     const bool warm = __double_as_longlong(state[64]) == DIIS_STATE_MAGIC && state[65] <= (double)(nd + 1);  // uniform
@@ -1051,16 +1053,16 @@ __global__ __launch_bounds__(64) void diis_solve8_lincomb_kernel(const double* _
         __syncthreads();
     }
     if (blockIdx.x == 0 && lane >= 1 && lane < m) coef[lane - 1] = c_out[lane];
-    double cf[7];
+    double cf[DIIS8_MAX_ND];
 #pragma unroll
-    for (int k = 0; k < 7; ++k) cf[k] = (k < nd) ? c_out[k + 1] : 0.0;
+    for (int k = 0; k < DIIS8_MAX_ND; ++k) cf[k] = (k < nd) ? c_out[k + 1] : 0.0;
 #pragma unroll
     for (int j = 0; j < DIIS8_PER_LANE; ++j) {
         const int64_t i = i0 + 64 * j;
         if (i < n) {
             double t = 0.0;
 #pragma unroll
-            for (int k = 0; k < 7; ++k)
+            for (int k = 0; k < DIIS8_MAX_ND; ++k)
                 if (k < nd) t = fma(cf[k], xv[j][k], t);
             out[i] = t;
         }
@@ -1193,6 +1195,36 @@ int finish_reduction(nbx_ctx* ctx, int nblocks, int nout, double* h_out) {
     return NBX_OK;
 }
 
+// ---- which kernel instance a size runs on: the ONLY statement of these limits.  The launch functions below call these,
+// and nbx_cycle_scalars_route / nbx_diis_route / nbx_vo_sumsq_route (include/nbx.h) report them to the tests.
+// The scalars kernel's four partial sums per T x T tile have to fit the context's scratch.
+inline bool scalars_tiles_fit(int64_t nao, int tile) {
+    const int64_t g = nbx_cdiv(nao, tile);
+    return g * g * 4 <= NBX_SCRATCH_DOUBLES - 64;
+}
+// the scalars of given matrices: 16 x 16 tiles while their partials fit (more workgroups for small N), 32 x 32 tiles
+// while those fit
+inline int scalars_route(int64_t nao) {
+    if (nao <= 0) return NBX_CYCLE_SCALARS_REFUSED;
+    if (scalars_tiles_fit(nao, 16)) return NBX_CYCLE_SCALARS_T16;
+    return scalars_tiles_fit(nao, TILE) ? NBX_CYCLE_SCALARS_T32 : NBX_CYCLE_SCALARS_REFUSED;
+}
+// the density made in the scalars kernel: 16 x 16 tiles, both spins occupied, at most DENS_MAX_NOCC orbitals each
+inline bool density_scalars_fused(int64_t nao, int64_t nocc_a, int64_t nocc_b) {
+    return scalars_route(nao) == NBX_CYCLE_SCALARS_T16 && nocc_a > 0 && nocc_b > 0 && nocc_a <= DENS_MAX_NOCC &&
+           nocc_b <= DENS_MAX_NOCC;
+}
+inline int diis_route(int64_t n, int64_t nd) {
+    if (n <= 0 || nd < 1 || nd > DIIS_MAX_SPACE) return NBX_DIIS_REFUSED;
+    return (nd <= DIIS8_MAX_ND && nbx_cdiv(n, 64 * DIIS8_PER_LANE) <= 65535) ? NBX_DIIS_FUSED : NBX_DIIS_GENERAL;
+}
+// (the orbital gradient of a cycle at N ~ 150 is 2 x 3800 numbers: one workgroup per spin writes its sum itself)
+inline int vo_sumsq_route(int64_t nao, int64_t nocc_a, int64_t nocc_b) {
+    if (nao <= 0 || nocc_a < 0 || nocc_a > nao || nocc_b < 0 || nocc_b > nao) return NBX_VO_SUMSQ_REFUSED;
+    const int64_t na = (nao - nocc_a) * nocc_a, nb = (nao - nocc_b) * nocc_b;
+    return (na > nb ? na : nb) <= 16384 ? NBX_VO_SUMSQ_ONE_WG : NBX_VO_SUMSQ_32_WG;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1251,7 +1283,7 @@ int nbx_huz_cycle_scalars(nbx_ctx* ctx, int64_t nao, const double* d_hcore, int 
     NBX_CHECK_ARG(ctx && d_hcore && d_vhf && d_hz && d_dm && d_dm_old && h_out && nao > 0);
     NBX_CHECK_ARG(hcore_ndim == 2 || hcore_ndim == 3);
     const int64_t g = nbx_cdiv(nao, TILE);
-    NBX_CHECK_ARG(g * g * 4 <= NBX_SCRATCH_DOUBLES - 64);
+    NBX_CHECK_ARG(scalars_tiles_fit(nao, TILE));
     hipLaunchKernelGGL(huz_scalars_kernel<TILE>, dim3((unsigned)g, (unsigned)g), dim3(TILE, 8), 0, ctx->stream, d_hcore,
                        hcore_ndim == 3 ? 1 : 0, d_vemb, d_vhf, d_hz, d_dm, d_dm_old, (int)nao, ctx->d_scratch);
     NBX_LAUNCH_CHECK();
@@ -1300,10 +1332,10 @@ int nbx_cycle_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, i
     NBX_CHECK_ARG(tail_n >= 0 && tail_n <= 64 && (tail_n == 0 || d_tail != nullptr));
     NBX_CHECK_ARG(dtail_n >= 0 && dtail_n <= 64 && (dtail_n == 0 || d_dtail != nullptr));
     NBX_CHECK_ARG(hcore_ndim == 2 || hcore_ndim == 3);
-    // 16 x 16 tiles while the partials fit the scratch (N <= 500): more workgroups for small N
-    const bool fine = nbx_cdiv(nao, 16) * nbx_cdiv(nao, 16) * 4 <= NBX_SCRATCH_DOUBLES - 64;
+    const int route = scalars_route(nao);  // 16 x 16 tiles while the partials fit the scratch: more workgroups for small N
+    NBX_CHECK_ARG(route != NBX_CYCLE_SCALARS_REFUSED);
+    const bool fine = route == NBX_CYCLE_SCALARS_T16;
     const int64_t g = nbx_cdiv(nao, fine ? 16 : TILE);
-    NBX_CHECK_ARG(g * g * 4 <= NBX_SCRATCH_DOUBLES - 64);
     if (fine)
         hipLaunchKernelGGL(huz_scalars_kernel<16>, dim3((unsigned)g, (unsigned)g), dim3(16, 8), 0, ctx->stream, d_hcore,
                            hcore_ndim == 3 ? 1 : 0, d_vemb, d_vhf, d_hz, d_dm, d_dm_old, (int)nao, ctx->d_scratch,
@@ -1320,15 +1352,14 @@ int nbx_cycle_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, i
 
 // The aufbau density D[x] = C[x][:, :nocc_x] C[x][:, :nocc_x]^T AND the scalars of the cycle that judge it, in one
 // launch (huz_scalars_kernel<16, true>): what nbx_gemm('N','T') + nbx_huz_cycle_scalars_dts give, bit for bit.
-// Returns NBX_E_UNSUPPORTED (nothing launched) where the fused form does not apply -- more than 64 occupied orbitals,
-// an empty spin, N > 500 -- and the caller takes the two launches.
+// Returns NBX_E_UNSUPPORTED (nothing launched) where the fused form does not apply -- more than DENS_MAX_NOCC occupied
+// orbitals, an empty spin, a size past the 16 x 16 tiles (density_scalars_fused) -- and the caller takes the two launches.
 int nbx_density_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, int hcore_ndim, const double* d_vemb,
                                const double* d_vhf, const double* d_hz, const double* d_c, int64_t nocc_a, int64_t nocc_b,
                                double* d_dm_out, const double* d_dm_old, double* d_out, const int* d_tail, int64_t tail_n,
                                double* d_dts) {
     NBX_CHECK_ARG(ctx && d_hcore && d_vhf && d_c && d_dm_out && d_dm_old && d_out && nao > 0);
-    const bool fine = nbx_cdiv(nao, 16) * nbx_cdiv(nao, 16) * 4 <= NBX_SCRATCH_DOUBLES - 64;
-    if (!fine || nocc_a <= 0 || nocc_b <= 0 || nocc_a > 64 || nocc_b > 64) return NBX_E_UNSUPPORTED;
+    if (!density_scalars_fused(nao, nocc_a, nocc_b)) return NBX_E_UNSUPPORTED;
     int m4 = 0, nb4 = d_dts ? s4_nb(nao) : 0, lpt4 = d_dts ? s4_lpt(nao) : 0;
     if (d_dts && (nbx_jk_m8_covers(nao) || nbx_jk_m4_covers(nao))) {
         int wl[4];
@@ -1390,7 +1421,7 @@ int nbx_diis_update_anti(nbx_ctx* ctx, int64_t n, int64_t space, int64_t slot, i
     hipLaunchKernelGGL(diis_push_kernel, dim3(blocks), dim3(256), 0, ctx->stream, n, (int)nd, (int)slot, d_x,
                        d_xprev, d_err, d_xs, d_es, ctx->d_scratch, d_coef + space, (int)anti_n);
     NBX_LAUNCH_CHECK();
-    if (nd <= 7 && nbx_cdiv(n, 64 * DIIS8_PER_LANE) <= 65535) {  // the usual case: solve and extrapolation in one launch
+    if (diis_route(n, nd) == NBX_DIIS_FUSED) {  // the usual case: solve and extrapolation in one launch
         hipLaunchKernelGGL(diis_solve8_lincomb_kernel, dim3((unsigned)nbx_cdiv(n, 64 * DIIS8_PER_LANE)), dim3(64), 0,
                            ctx->stream, ctx->d_scratch, (int)blocks, (int)nd, (int)slot, d_h, (int)(space + 1), d_coef,
                            d_coef + space, n, d_xs, n, d_xprev);
@@ -1410,9 +1441,7 @@ extern "C" {
 
 int nbx_vo_sumsq(nbx_ctx* ctx, int64_t nao, const double* d_fmo, int64_t nocc_a, int64_t nocc_b, double* d_out) {
     NBX_CHECK_ARG(ctx && d_fmo && d_out && nao > 0 && nocc_a >= 0 && nocc_a <= nao && nocc_b >= 0 && nocc_b <= nao);
-    // (the orbital gradient of a cycle at N ~ 150 is 2 x 3800 numbers: one workgroup per spin writes its sum itself)
-    const int64_t na = (nao - nocc_a) * nocc_a, nb = (nao - nocc_b) * nocc_b;
-    if ((na > nb ? na : nb) <= 16384) {
+    if (vo_sumsq_route(nao, nocc_a, nocc_b) == NBX_VO_SUMSQ_ONE_WG) {
         hipLaunchKernelGGL(vo_sumsq_kernel, dim3(1, 2), dim3(256), 0, ctx->stream, d_fmo, (int)nao, (int)nocc_a, (int)nocc_b,
                            d_out);
         NBX_LAUNCH_CHECK();
@@ -1426,6 +1455,15 @@ int nbx_vo_sumsq(nbx_ctx* ctx, int64_t nao, const double* d_fmo, int64_t nocc_a,
     NBX_LAUNCH_CHECK();
     return NBX_OK;
 }
+
+int nbx_cycle_scalars_route(int64_t nao, int64_t nocc_a, int64_t nocc_b) {
+    if (nocc_a >= 0 && nocc_b >= 0 && density_scalars_fused(nao, nocc_a, nocc_b)) return NBX_CYCLE_SCALARS_T16_DENS;
+    return scalars_route(nao);
+}
+
+int nbx_diis_route(int64_t n, int64_t nd) { return diis_route(n, nd); }
+
+int nbx_vo_sumsq_route(int64_t nao, int64_t nocc_a, int64_t nocc_b) { return vo_sumsq_route(nao, nocc_a, nocc_b); }
 
 int nbx_axpby(nbx_ctx* ctx, int64_t n, double a, const double* d_x, double b, double* d_y) {
     NBX_CHECK_ARG(ctx && n >= 0);
