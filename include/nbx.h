@@ -57,9 +57,6 @@ typedef struct nbx_ctx nbx_ctx;
 
 /* ------------------------------------------------------------------ context */
 int nbx_version(void);
-/* 1 for a `make EXPERIMENTAL=1` build (the J/K experiments of DESIGN.md section 9 are linked in and selectable
- * through the environment), 0 for the shipped library. */
-int nbx_experimental(void);
 const char* nbx_last_error(void);
 int nbx_device_count(int* count);
 /* stream: the hipStream_t to launch on (e.g. torch's current stream; NULL = the device's
@@ -167,9 +164,7 @@ int nbx_jk_dense_sym(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const do
  * lower triangle of its (r,s) matrix cut into NB = 2 (N <= 128) or 4 blocks of s = N/NB rows:
  * first the NB diagonal triangles (row-major, packed), then for r = 1..NB-1 the rectangles
  * (I, J = I ^ r), I > J, ordered by the row block I, row-major with row stride s|1 (zero pad); each
- * of the NB chunks padded to an even number of doubles.  (With NBX_JK_P8=1 in the environment whole
- * tensors of N = 100..156, N % 4 == 0 are stored 8-fold instead -- of every tile only the entries
- * (r,s) <= (p,q), csrc/jk_p8.hip; same entry points and results, experimental: DESIGN.md section 9.)
+ * of the NB chunks padded to an even number of doubles.
  * N = 100, 104, ..., 148 have a layout and a kernel of their own (csrc/jk_m4.hip, one instance per size, the contraction on
  * v_mfma_f64_4x4x4_4b_f64; N = 97 .. 147 that are not multiples of four run as the next multiple with the extra rows and
  * columns zero -- the padding is internal, as for jk_s4.hip's padded sizes): a tile is the
@@ -208,7 +203,8 @@ int nbx_jk_packed(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const doubl
 
 /* Test support: which file's kernel nbx_eri_pack / nbx_jk_packed serve a size with IN THIS PROCESS (the switches
  * NBX_JK_M8 / NBX_JK_M4 / NBX_JK_MX are read once per process) and the instance size it runs as (nao itself, or the
- * next instance with zero rows and columns; 0 with NBX_JK_KERNEL_NONE) -- the functions the launcher asks, host
+ * next instance with zero rows and columns; 0 with NBX_JK_KERNEL_NONE) -- the answer of the one resolver
+ * (csrc/jk_packed.hip, packed_resolve) that honours the switches and that every entry point above asks, host
  * arithmetic only (no context, no GPU).  tests/jk_cases.py keeps a size per instance and tests/test_host_jk_cases.py
  * fails when a size of the table moves to another kernel.                                                        */
 #define NBX_JK_KERNEL_NONE 0   /* not covered: nbx_jk_dense_sym */

@@ -5,6 +5,7 @@
 // reductions for the scalar outputs.
 #include "nbx_common.h"
 #include "jk_m4_layout.h"
+#include "jk_packed.h"
 #include "jk_s4_layout.h"
 
 namespace {
@@ -1319,16 +1320,8 @@ int nbx_cycle_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, i
                              double* d_out, const int* d_tail, int64_t tail_n, double* d_dts, const double* d_dtail,
                              int64_t dtail_n) {
     NBX_CHECK_ARG(ctx && d_hcore && d_vhf && d_dm && d_dm_old && d_out && nao > 0);
-    int m4 = 0, nb4 = d_dts ? s4_nb(nao) : 0, lpt4 = d_dts ? s4_lpt(nao) : 0;
-    if (d_dts && (nbx_jk_m8_covers(nao) || nbx_jk_m4_covers(nao))) {  // (the table in jk_m4.hip's / jk_m8.hip's order: its layout parameters travel in these three)
-        int wl[4];
-        if (nbx_jk_m8_covers(nao)) nbx_jk_m8_weight_layout(nao, wl);
-        else nbx_jk_m4_weight_layout(nao, wl);
-        nb4 = wl[0];
-        lpt4 = wl[1];
-        m4 = (wl[2] << 8) | wl[3];
-    }
-    NBX_CHECK_ARG(d_dts == nullptr || lpt4 > 0);  // the table exists for sizes nbx_jk_packed covers
+    int nb4 = 0, lpt4 = 0, m4 = 0;  // the table's layout, in the order of the kernel that reads it (jk_packed.hip)
+    NBX_CHECK_ARG(d_dts == nullptr || nbx_jk_dts_layout(nao, &nb4, &lpt4, &m4) > 0);  // the table exists where nbx_jk_dts_bytes > 0
     NBX_CHECK_ARG(tail_n >= 0 && tail_n <= 64 && (tail_n == 0 || d_tail != nullptr));
     NBX_CHECK_ARG(dtail_n >= 0 && dtail_n <= 64 && (dtail_n == 0 || d_dtail != nullptr));
     NBX_CHECK_ARG(hcore_ndim == 2 || hcore_ndim == 3);
@@ -1360,16 +1353,8 @@ int nbx_density_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore,
                                double* d_dts) {
     NBX_CHECK_ARG(ctx && d_hcore && d_vhf && d_c && d_dm_out && d_dm_old && d_out && nao > 0);
     if (!density_scalars_fused(nao, nocc_a, nocc_b)) return NBX_E_UNSUPPORTED;
-    int m4 = 0, nb4 = d_dts ? s4_nb(nao) : 0, lpt4 = d_dts ? s4_lpt(nao) : 0;
-    if (d_dts && (nbx_jk_m8_covers(nao) || nbx_jk_m4_covers(nao))) {
-        int wl[4];
-        if (nbx_jk_m8_covers(nao)) nbx_jk_m8_weight_layout(nao, wl);
-        else nbx_jk_m4_weight_layout(nao, wl);
-        nb4 = wl[0];
-        lpt4 = wl[1];
-        m4 = (wl[2] << 8) | wl[3];
-    }
-    NBX_CHECK_ARG(d_dts == nullptr || lpt4 > 0);
+    int nb4 = 0, lpt4 = 0, m4 = 0;
+    NBX_CHECK_ARG(d_dts == nullptr || nbx_jk_dts_layout(nao, &nb4, &lpt4, &m4) > 0);
     NBX_CHECK_ARG(tail_n >= 0 && tail_n <= 64 && (tail_n == 0 || d_tail != nullptr));
     NBX_CHECK_ARG(hcore_ndim == 2 || hcore_ndim == 3);
     const int64_t g = nbx_cdiv(nao, 16);

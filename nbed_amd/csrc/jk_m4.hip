@@ -39,7 +39,7 @@
 
 #include "jk_m4_layout.h"
 #include "jk_m4_walk.h"
-#include "nbx_common.h"
+#include "jk_packed.h"
 
 // (m0 is named as a clobber of the LDS-DMA asm below; clang calls that a reserved register)
 #pragma clang diagnostic ignored "-Winline-asm"

@@ -24,7 +24,7 @@
 
 #include "jk_m8_layout.h"
 #include "jk_m4_walk.h"
-#include "nbx_common.h"
+#include "jk_packed.h"
 
 #pragma clang diagnostic ignored "-Winline-asm"
 

@@ -22,7 +22,7 @@
 
 #include "jk_m4_layout.h"
 #include "jk_m4_walk.h"
-#include "nbx_common.h"
+#include "jk_packed.h"
 
 #pragma clang diagnostic ignored "-Winline-asm"
 
@@ -539,12 +539,6 @@ int mx_run(nbx_ctx* ctx, int64_t p0, int64_t p1, const double* d_packed, const d
         default: break;                  \
     }
 #ifdef MX_HAS_HI
-bool nbx_jk_mx_covers_hi(int64_t N);
-size_t nbx_jk_mx_packed_bytes_hi(int64_t N, int64_t p0, int64_t p1);
-size_t nbx_jk_mx_worksize_hi(int64_t N, int64_t p0, int64_t p1, int64_t ndm);
-int nbx_jk_mx_pack_hi(nbx_ctx* ctx, int64_t N, int64_t nsrc, int64_t p0, int64_t p1, const double* d_eri, double* d_packed);
-int nbx_jk_mx_hi(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
-                 double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf);
 #define MX_ELSE_HI(call) return call;
 #else
 #define MX_ELSE_HI(call)
@@ -602,11 +596,11 @@ int MX_FN(nbx_jk_mx_pack)(nbx_ctx* ctx, int64_t N, int64_t nsrc, int64_t p0, int
 }
 
 int MX_FN(nbx_jk_mx)(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
-                     double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf) {
+                     double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double*) {
     NBX_CHECK_ARG(MX_FN(nbx_jk_mx_covers)(N));
 #define MX_CASE_run(NB_) case NB_: return mx_run<NB_>(ctx, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf);
     MX_DISPATCH(N, run)
 #undef MX_CASE_run
-    MX_ELSE_HI(nbx_jk_mx_hi(ctx, N, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf))
+    MX_ELSE_HI(nbx_jk_mx_hi(ctx, N, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, nullptr))
     return NBX_E_UNSUPPORTED;
 }

@@ -1,4 +1,5 @@
-// libnbx: J/K contraction on 4-fold packed integrals (include/nbx.h "J/K contraction, packed form").
+// libnbx: J/K contraction on 4-fold packed integrals (include/nbx.h "J/K contraction, packed form"): the back-end
+// (jk_packed.h) that walks the tiles on the vector ALU; jk_packed.hip decides which sizes it is handed.
 //
 //   (pq|rs) = (qp|rs) = (pq|sr): only the pairs q <= p AND s <= r are stored and read -- a quarter
 //   of the dense tensor, half of what jk_sym.hip reads.  (PySCF keeps `mf._eri` 8-fold packed and
@@ -26,84 +27,10 @@
 // Work distribution, partial buffers and the final reduction are those of jk_sym.hip: persistent
 // workgroups own equal contiguous ranges of the tile sequence T(p,q) = p(p+1)/2 + q; everything
 // is summed in a fixed order (bitwise reproducible).  The slab interface is additive.
-#include <cstdlib>
-
 #include "nbx_common.h"
 #include "jk_s4_layout.h"
 #include "jk_s4_device.h"
-
-// The EXPERIMENTAL forms of the packed kernel (parity green, none measurably faster than the
-// kernel in this file) are linked only into a `make EXPERIMENTAL=1` build, where the environment
-// selects them (NBX_JK_M4 / NBX_JK_P8 / NBX_JK_S8 / NBX_JK_DMA); the shipped library holds what runs.
-// jk_m4.hip: the walk on the matrix cores (v_mfma_f64_4x4x4_4b_f64, block-major swizzled tiles streamed into LDS by the
-// load unit, loading / walking waves): serves N = 148 (the size it is instantiated for) unless NBX_JK_M4=0 -- 0.87 of this
-// file's kernel time there
-bool nbx_jk_m4_covers(int64_t N);
-size_t nbx_jk_m4_weights_bytes(int64_t N);
-size_t nbx_jk_m4_packed_bytes(int64_t N, int64_t p0, int64_t p1);
-size_t nbx_jk_m4_worksize(int64_t N, int64_t p0, int64_t p1, int64_t ndm);
-int nbx_jk_m4_pack(nbx_ctx* ctx, int64_t N, int64_t nsrc, int64_t p0, int64_t p1, const double* d_eri, double* d_packed);
-int nbx_jk_m4(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
-              double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_wt);
-// jk_m8.hip: the 8-fold packed form (every integral once) for the sizes it has an instance for, unless NBX_JK_M8=0
-bool nbx_jk_m8_covers(int64_t N);
-void nbx_jk_m8_weight_layout(int64_t N, int out[4]);
-size_t nbx_jk_m8_weights_bytes(int64_t N);
-size_t nbx_jk_m8_packed_bytes(int64_t N, int64_t p0, int64_t p1);
-size_t nbx_jk_m8_worksize(int64_t N, int64_t p0, int64_t p1, int64_t ndm);
-int nbx_jk_m8_pack(nbx_ctx* ctx, int64_t N, int64_t nsrc, int64_t p0, int64_t p1, const double* d_eri, double* d_packed);
-int nbx_jk_m8(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
-              double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_wt);
-// jk_mx.hip: the same walk for the sizes above (N = 152 .. 288, a tile in 4 .. 20 chunks), unless NBX_JK_MX=0
-bool nbx_jk_mx_covers(int64_t N);
-int64_t nbx_jk_mx_padded(int64_t N);
-size_t nbx_jk_mx_packed_bytes(int64_t N, int64_t p0, int64_t p1);
-size_t nbx_jk_mx_worksize(int64_t N, int64_t p0, int64_t p1, int64_t ndm);
-int nbx_jk_mx_pack(nbx_ctx* ctx, int64_t N, int64_t nsrc, int64_t p0, int64_t p1, const double* d_eri, double* d_packed);
-int nbx_jk_mx(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
-              double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf);
-#ifdef NBX_EXPERIMENTAL
-// jk_p8.hip: the 8-fold form (truncated tiles) that serves whole tensors of the NB = 4 / six-loads sizes
-bool nbx_jk_p8_covers(int64_t N, int64_t p0, int64_t p1);
-size_t nbx_jk_p8_packed_bytes(int64_t N);
-size_t nbx_jk_p8_worksize(int64_t N, int64_t ndm);
-int nbx_jk_p8_pack(nbx_ctx* ctx, int64_t N, const double* d_eri, double* d_packed);
-int nbx_jk_p8(nbx_ctx* ctx, int64_t N, const double* d_packed, const double* d_dm, int64_t ndm, double* d_jk, void* d_work,
-              const double* d_hv, double* d_fock, double* d_vhf, const double* d_dts_in);
-
-// jk_s8.hip: the eight-wave, matrix-pipe form of the NB = 4 / six-loads instance
-bool nbx_jk_s8_covers(int64_t N);
-void nbx_jk_s8_plan(int64_t ntiles, int* wgs, int* L, int* S);
-int nbx_jk_s8_launch(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t np, int64_t ndm, const double* d_packed,
-                     const double* d_dm, const double* d_dts, double* d_j, double* k1, double* k2, int64_t t_begin,
-                     int64_t t_end, int wgs, int L, int S);
-
-// jk_s4d.hip: the NB = 4 / six-loads instance with the tiles streamed straight into LDS
-bool nbx_jk_s4d_covers(int NB, int lpt);
-size_t nbx_jk_s4d_lds_bytes(int NB, int lpt, int variant);
-int nbx_jk_s4d_per_cu(int variant);
-int nbx_jk_s4d_launch(nbx_ctx* ctx, int variant, int64_t N, int64_t p0, int64_t np, int64_t ndm, int lpt,
-                      const double* d_packed, const double* d_dm, const double* d_dts, double* d_j, double* k1, double* k2,
-                      int64_t t_begin, int64_t t_end, int wgs, int L, int S);
-#else
-static inline bool nbx_jk_p8_covers(int64_t, int64_t, int64_t) { return false; }
-static inline size_t nbx_jk_p8_packed_bytes(int64_t) { return 0; }
-static inline size_t nbx_jk_p8_worksize(int64_t, int64_t) { return 0; }
-static inline int nbx_jk_p8_pack(nbx_ctx*, int64_t, const double*, double*) { return NBX_E_UNSUPPORTED; }
-static inline int nbx_jk_p8(nbx_ctx*, int64_t, const double*, const double*, int64_t, double*, void*, const double*, double*,
-                            double*, const double*) { return NBX_E_UNSUPPORTED; }
-static inline bool nbx_jk_s8_covers(int64_t) { return false; }
-static inline void nbx_jk_s8_plan(int64_t, int*, int*, int*) {}
-static inline int nbx_jk_s8_launch(nbx_ctx*, int64_t, int64_t, int64_t, int64_t, const double*, const double*, const double*,
-                                   double*, double*, double*, int64_t, int64_t, int, int, int) { return NBX_E_UNSUPPORTED; }
-static inline bool nbx_jk_s4d_covers(int, int) { return false; }
-static inline size_t nbx_jk_s4d_lds_bytes(int, int, int) { return 0; }
-static inline int nbx_jk_s4d_per_cu(int) { return 2; }
-static inline int nbx_jk_s4d_launch(nbx_ctx*, int, int64_t, int64_t, int64_t, int64_t, int, const double*, const double*,
-                                    const double*, double*, double*, double*, int64_t, int64_t, int, int, int) {
-    return NBX_E_UNSUPPORTED;
-}
-#endif
+#include "jk_packed.h"
 
 namespace {
 
@@ -121,20 +48,6 @@ __global__ __launch_bounds__(256) void s4_pack_kernel(const double* __restrict__
     double* dst = out + (int64_t)blockIdx.x * g.M;
     for (int a = 0; a < N; ++a)
         for (int b = threadIdx.x; b <= a; b += blockDim.x) dst[s4_flat(g, a, b)] = src[(int64_t)a * N + b];
-}
-
-// (nmat, N, N) -> (nmat, NP, NP) with zero rows/columns appended, and back
-__global__ void s4_pad_square_kernel(const double* __restrict__ src, double* __restrict__ dst, int N, int NP, int nmat) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)nmat * NP * NP) return;
-    const int b = (int)(i % NP), a = (int)((i / NP) % NP), m = (int)(i / ((int64_t)NP * NP));
-    dst[i] = (a < N && b < N) ? src[((int64_t)m * N + a) * N + b] : 0.0;
-}
-__global__ void s4_crop_square_kernel(const double* __restrict__ src, double* __restrict__ dst, int N, int NP, int nmat) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)nmat * N * N) return;
-    const int b = (int)(i % N), a = (int)((i / N) % N), m = (int)(i / ((int64_t)N * N));
-    dst[i] = src[((int64_t)m * NP + a) * NP + b];
 }
 
 // Dtot' in the order the staging slots hold the tile: dts[ch][w][k][lane] = the pair of
@@ -325,34 +238,7 @@ __global__ __launch_bounds__(NB * 64) __attribute__((amdgpu_waves_per_eu(WV, WV)
     if (tid == 0) store_j(par ^ 1, pj, qj);
 }
 
-}  // namespace
-
-// the Dtot' table of a density (shared with jk_p8.hip, which keeps the table's format)
-int nbx_jk_s4_dtot(nbx_ctx* ctx, int64_t N, const double* d_dm, int64_t ndm, double* d_dts) {
-    const int NB = s4_nb(N), lpt = s4_lpt(N);
-    hipLaunchKernelGGL(s4_dtot_kernel, dim3((unsigned)nbx_cdiv(NB * NB * lpt * 64, 256)), dim3(256), 0, ctx->stream, d_dm,
-                       d_dts, (int)N, NB, lpt, (int)ndm);
-    NBX_LAUNCH_CHECK();
-    return NBX_OK;
-}
-
-namespace {
-
-bool s4_use_s8(int64_t N) {
-    // jk_s8.hip is EXPERIMENTAL: parity-tested, but measured 5-15 % slower than the four-wave VALU kernel
-    // below -- opt in with NBX_JK_S8=1
-    static const bool on = getenv("NBX_JK_S8") != nullptr;
-    return on && nbx_jk_s8_covers(N);
-}
-
-int s4_use_dma(int NB, int lpt) {  // 0: off; 1-3: the variants of jk_s4d.hip (A/B switch while they are measured)
-    static const int v = getenv("NBX_JK_DMA") ? atoi(getenv("NBX_JK_DMA")) : 0;
-    return (v >= 1 && v <= 3 && nbx_jk_s4d_covers(NB, lpt)) ? v : 0;
-}
-
 struct S4Plan {
-    bool s8;
-    int dma;
     int NB, lpt, wgs, L, S, per_cu;
     size_t lds_bytes, dtp_off, k1_off, k2_off, total;
     S4Geom g;
@@ -368,11 +254,9 @@ S4Plan s4_plan(int64_t N, int64_t p0, int64_t np, int64_t ndm) {
     pl.lpt = s4_lpt_class((int)nbx_cdiv((pl.g.E0 > pl.g.Er ? pl.g.E0 : pl.g.Er) / 2, nt), pl.NB);
     // chunk buffers, slack, J partials
     pl.lds_bytes = (size_t)(2 * pl.lpt * nt * 2 + 128 + 2 * pl.NB) * sizeof(double);
-    pl.dma = s4_use_dma(pl.NB, pl.lpt);
-    if (pl.dma) pl.lds_bytes = nbx_jk_s4d_lds_bytes(pl.NB, pl.lpt, pl.dma);
     int64_t per_cu = (int64_t)(S4_LDS_PER_CU / (pl.lds_bytes + 256));
     // two waves per SIMD (the staging registers need the budget), one for the long-row instances
-    const int64_t by_waves = pl.dma ? nbx_jk_s4d_per_cu(pl.dma) : (pl.lpt >= 10 ? 4 : 8) / pl.NB;
+    const int64_t by_waves = (pl.lpt >= 10 ? 4 : 8) / pl.NB;
     if (per_cu > by_waves) per_cu = by_waves;
     if (per_cu < 1) per_cu = 1;
     pl.per_cu = (int)per_cu;
@@ -383,8 +267,6 @@ S4Plan s4_plan(int64_t N, int64_t p0, int64_t np, int64_t ndm) {
     pl.L = (int)L;
     pl.wgs = (int)nbx_cdiv(ntiles, L);
     pl.S = (int)sqrt(2.0 * (double)L) + 3;
-    pl.s8 = s4_use_s8(N);
-    if (pl.s8) nbx_jk_s8_plan(ntiles, &pl.wgs, &pl.L, &pl.S);  // one eight-wave workgroup per CU
     size_t off = 0;
     pl.dtp_off = off; off += s4_align256((size_t)(pl.NB * pl.NB * pl.lpt * 128) * sizeof(double));
     pl.k1_off = off; off += s4_align256((size_t)((int64_t)pl.wgs * pl.S * ndm * N) * sizeof(double));
@@ -395,258 +277,28 @@ S4Plan s4_plan(int64_t N, int64_t p0, int64_t np, int64_t ndm) {
 
 }  // namespace
 
-// The size jk_m4.hip runs nao as: nao itself or the next multiple of four (at most three zero rows / columns more), if that
-// size has an instance; 0: jk_s4.hip's business
-static int64_t m4_padded(int64_t nao) {
-    const int64_t n4 = (nao + 3) / 4 * 4;
-    return (nao > 0 && nbx_jk_m4_covers(n4)) ? n4 : 0;
+// ---- the back-end interface (jk_packed.h)
+bool nbx_jk_s4_covers(int64_t N) { return s4_supported(N); }
+
+size_t nbx_jk_s4_packed_bytes(int64_t N, int64_t p0, int64_t p1) {
+    return (size_t)((s4_tri(p1) - s4_tri(p0)) * s4_geom((int)N, s4_nb(N)).M) * sizeof(double);
 }
 
-// the same for jk_m8.hip (the 8-fold form of these sizes; it takes them when it has the instance)
-static int64_t m8_padded(int64_t nao) {
-    const int64_t n4 = (nao + 3) / 4 * 4;
-    return (nao > 0 && nbx_jk_m8_covers(n4)) ? n4 : 0;
-}
+size_t nbx_jk_s4_worksize(int64_t N, int64_t p0, int64_t p1, int64_t ndm) { return s4_plan(N, p0, p1 - p0, ndm).total; }
 
-// the size jk_mx.hip runs nao as (nao itself or the next instance, at most eight zero rows / columns more); 0: none
-static int64_t mx_padded(int64_t nao) { return (nao > 0 && !m4_padded(nao)) ? nbx_jk_mx_padded(nao) : 0; }
-
-// 1: a kernel instance serves N; 2: served as the next covered size with zero rows/columns; 0: no
-extern "C" int nbx_jk_packed_supported(int64_t nao) {
-    if (const int64_t nx = mx_padded(nao)) return nx == nao ? 1 : 2;
-    return s4_supported(nao) ? 1 : (s4_padded(nao) > 0 ? 2 : 0);
-}
-
-extern "C" int nbx_jk_packed_fold(int64_t nao) {
-    if (nbx_jk_packed_supported(nao) == 0) return 0;
-    return m8_padded(nao) ? 8 : 4;
-}
-
-// Test support (include/nbx.h): which file's kernel s4_jk hands nao to in this process and the instance size it runs as --
-// asked of the functions s4_jk, nbx_eri_pack and nbx_jk_packed_worksize ask, in their order.
-bool nbx_jk_mx_covers_hi(int64_t N);  // (jk_mx_hi.hip: the instances of the second translation unit)
-extern "C" int nbx_jk_packed_route(int64_t nao, int* kernel, int* run_as) {
-    if (kernel == nullptr || run_as == nullptr) return NBX_E_INVALID;
-    int k = NBX_JK_KERNEL_NONE;
-    int64_t n = 0;
-    if (const int64_t nx = mx_padded(nao)) {
-        k = nbx_jk_mx_covers_hi(nx) ? NBX_JK_KERNEL_MX_HI : NBX_JK_KERNEL_MX;
-        n = nx;
-    } else if (const int64_t np = s4_padded(nao)) {
-        if (const int64_t n8 = m8_padded(nao)) {
-            k = NBX_JK_KERNEL_M8;
-            n = n8;
-        } else if (const int64_t n4 = m4_padded(nao)) {
-            k = NBX_JK_KERNEL_M4;
-            n = n4;
-        } else {
-            k = NBX_JK_KERNEL_S4;
-            n = np;
-        }
-    }
-    *kernel = k;
-    *run_as = (int)n;
-    return NBX_OK;
-}
-
-extern "C" size_t nbx_eri_packed_bytes(int64_t nao, int64_t p0, int64_t p1) {
-    if (p0 < 0 || p1 < p0 || p1 > nao) return 0;
-    if (const int64_t nx = mx_padded(nao)) return nbx_jk_mx_packed_bytes(nx, p0, p1);
-    const int64_t NP = s4_padded(nao);
-    if (NP == 0) return 0;
-    if (const int64_t n8 = m8_padded(nao)) return nbx_jk_m8_packed_bytes(n8, p0, p1);
-    if (m4_padded(nao)) return nbx_jk_m4_packed_bytes(m4_padded(nao), p0, p1);
-    if (nbx_jk_p8_covers(nao, p0, p1)) return nbx_jk_p8_packed_bytes(nao);
-    const S4Geom g = s4_geom((int)NP, s4_nb(NP));
-    return (size_t)((s4_tri(p1) - s4_tri(p0)) * g.M) * sizeof(double);
-}
-
-extern "C" int nbx_eri_pack(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_eri, double* d_packed) {
-    NBX_CHECK_ARG(ctx);
-    NBX_CHECK_ARG(nao > 0 && p0 >= 0 && p1 >= p0 && p1 <= nao);
-    if (const int64_t nx = mx_padded(nao)) {
-        if (p0 == p1) return NBX_OK;
-        NBX_CHECK_ARG(d_eri && d_packed);
-        return nbx_jk_mx_pack(ctx, nx, nao, p0, p1, d_eri, d_packed);
-    }
-    const int64_t NP = s4_padded(nao);  // the tiles (p, q) with p < nao of the padded tensor: the others are zero
-    if (NP == 0) {
-        nbx_set_error("nbx_eri_pack: N = %lld is not covered by the packed J/K kernel", (long long)nao);
-        return NBX_E_UNSUPPORTED;
-    }
-    if (p0 == p1) return NBX_OK;
-    NBX_CHECK_ARG(d_eri && d_packed);
-    if (const int64_t n8 = m8_padded(nao)) return nbx_jk_m8_pack(ctx, n8, nao, p0, p1, d_eri, d_packed);
-    if (m4_padded(nao)) return nbx_jk_m4_pack(ctx, m4_padded(nao), nao, p0, p1, d_eri, d_packed);
-    if (nbx_jk_p8_covers(nao, p0, p1)) return nbx_jk_p8_pack(ctx, nao, d_eri, d_packed);
-    const int64_t ntiles = s4_tri(p1) - s4_tri(p0);
-    int rc = nbx_memset(ctx, d_packed, 0, nbx_eri_packed_bytes(nao, p0, p1));
+int nbx_jk_s4_pack(nbx_ctx* ctx, int64_t N, int64_t nsrc, int64_t p0, int64_t p1, const double* d_eri, double* d_packed) {
+    const int rc = nbx_memset(ctx, d_packed, 0, nbx_jk_s4_packed_bytes(N, p0, p1));
     if (rc != NBX_OK) return rc;
-    hipLaunchKernelGGL(s4_pack_kernel, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, d_eri, d_packed, (int)nao,
-                       (int)NP, s4_nb(NP), (int)p0, s4_tri(p0));
+    hipLaunchKernelGGL(s4_pack_kernel, dim3((unsigned)(s4_tri(p1) - s4_tri(p0))), dim3(256), 0, ctx->stream, d_eri, d_packed,
+                       (int)nsrc, (int)N, s4_nb(N), (int)p0, s4_tri(p0));
     NBX_LAUNCH_CHECK();
     return NBX_OK;
 }
 
-extern "C" size_t nbx_jk_packed_worksize(int64_t nao, int64_t p0, int64_t p1, int64_t ndm) {
-    if (p0 < 0 || p1 < p0 || p1 > nao || ndm <= 0) return 0;
-    if (const int64_t nx = mx_padded(nao))  // (+ the padded densities and J/K of a size that is not an instance)
-        return nbx_jk_mx_worksize(nx, p0, p1, ndm) + (nx != nao ? s4_align256((size_t)((1 + 2 * ndm) * nx * nx) * sizeof(double)) : 0);
-    const int64_t NP = s4_padded(nao);
-    if (NP == 0) return 0;
-    if (const int64_t n8 = m8_padded(nao))  // (+ the padded densities and J/K of a size that is not a multiple of four)
-        return nbx_jk_m8_worksize(n8, p0, p1, ndm) + (n8 != nao ? s4_align256((size_t)((1 + 2 * ndm) * n8 * n8) * sizeof(double)) : 0);
-    if (const int64_t n4 = m4_padded(nao))  // (+ the padded densities and J/K of a size that is not a multiple of four)
-        return nbx_jk_m4_worksize(n4, p0, p1, ndm) + (n4 != nao ? s4_align256((size_t)((1 + 2 * ndm) * n4 * n4) * sizeof(double)) : 0);
-    if (nbx_jk_p8_covers(nao, p0, p1)) return nbx_jk_p8_worksize(nao, ndm);
-    size_t total = s4_plan(NP, p0, p1 - p0, ndm).total;
-    if (NP != nao) total += s4_align256((size_t)((1 + 2 * ndm) * NP * NP) * sizeof(double));  // padded D and J/K
-    return total;
-}
-
-static int s4_jk(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm,
-                 int64_t ndm, double* d_jk, void* d_work, size_t work_bytes, const double* d_hv, double* d_fock,
-                 double* d_vhf, const double* d_dts = nullptr);
-static int s4_jk_native(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm,
-                        int64_t ndm, double* d_jk, void* d_work, size_t work_bytes, const double* d_hv,
-                        double* d_fock, double* d_vhf, const double* d_dts);
-
-extern "C" size_t nbx_jk_dts_bytes(int64_t nao) {
-    if (mx_padded(nao)) return 0;  // (jk_mx.hip prepares its table itself: one small launch beside a build of 0.2 .. 2.4 ms)
-    if (nbx_jk_m8_covers(nao)) {  // (jk_m8.hip: jk_m4.hip's staging order with its own chunk boundaries when it has four chunks)
-        int wl[4];
-        nbx_jk_m8_weight_layout(nao, wl);
-        return wl[3] ? nbx_jk_m8_weights_bytes(nao) : 0;
-    }
-    if (nbx_jk_m4_covers(nao)) return nbx_jk_m4_weights_bytes(nao);  // (the same table in jk_m4.hip's staging order)
-    if (!s4_supported(nao)) return 0;  // (zero-padded sizes build their table themselves)
-    const int NB = s4_nb(nao);
-    return (size_t)(NB * NB * s4_lpt(nao) * 128) * sizeof(double);
-}
-
-extern "C" int nbx_jk_dts_init(nbx_ctx* ctx, int64_t nao, double* d_dts) {
-    NBX_CHECK_ARG(ctx && d_dts && s4_supported(nao) && !mx_padded(nao));
-    return nbx_memset(ctx, d_dts, 0, nbx_jk_dts_bytes(nao));
-}
-
-extern "C" int nbx_jk_packed(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_packed,
-                             const double* d_dm, int64_t ndm, double* d_jk, void* d_work, size_t work_bytes) {
-    return s4_jk(ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, work_bytes, nullptr, nullptr, nullptr);
-}
-
-extern "C" int nbx_jk_packed_fock(nbx_ctx* ctx, int64_t nao, const double* d_packed, const double* d_dm,
-                                  const double* d_hv, double* d_jk, double* d_fock, double* d_vhf, void* d_work,
-                                  size_t work_bytes, const double* d_dts) {
-    NBX_CHECK_ARG(d_hv && d_fock);
-    return s4_jk(ctx, nao, 0, nao, d_packed, d_dm, 2, d_jk, d_work, work_bytes, d_hv, d_fock, d_vhf, d_dts);
-}
-
-static int s4_jk(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm,
-                 int64_t ndm, double* d_jk, void* d_work, size_t work_bytes, const double* d_hv, double* d_fock,
-                 double* d_vhf, const double* d_dts) {
-    NBX_CHECK_ARG(ctx && d_dm && d_jk);
-    NBX_CHECK_ARG(nao > 0 && p0 >= 0 && p1 >= p0 && p1 <= nao);
-    NBX_CHECK_ARG(d_packed != nullptr || p0 == p1);
-    NBX_CHECK_ARG(ndm == 1 || ndm == 2);
-    const int64_t NX = mx_padded(nao);
-    const int64_t NPAD = NX ? NX : s4_padded(nao);
-    if (NPAD == 0) {
-        nbx_set_error("nbx_jk_packed: N = %lld is not covered (N <= 288 within %d of a size the kernels have an "
-                      "instance for)", (long long)nao, S4_MAX_PAD);
-        return NBX_E_UNSUPPORTED;
-    }
-    const size_t need = nbx_jk_packed_worksize(nao, p0, p1, ndm);
-    if (d_work == nullptr || work_bytes < need) {
-        nbx_set_error("nbx_jk_packed: workspace %zu < %zu bytes", work_bytes, need);
-        return NBX_E_NOMEM;
-    }
-    NBX_CHECK_ARG((reinterpret_cast<uintptr_t>(d_packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0);
-    if (p1 == p0) return nbx_memset(ctx, d_jk, 0, (size_t)((1 + ndm) * nao * nao) * sizeof(double));
-    if (NX == nao) return nbx_jk_mx(ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf);
-    if (NX) {
-        // as the NX x NX problem whose extra rows and columns are zero (tiles with p >= nao are neither stored nor visited)
-        char* tail = static_cast<char*>(d_work) + nbx_jk_mx_worksize(NX, p0, p1, ndm);
-        double* dm_pad = reinterpret_cast<double*>(tail);
-        double* jk_pad = dm_pad + ndm * NX * NX;
-        const int64_t tin = ndm * NX * NX, tout = (1 + ndm) * nao * nao;
-        hipLaunchKernelGGL(s4_pad_square_kernel, dim3((unsigned)nbx_cdiv(tin, 256)), dim3(256), 0, ctx->stream, d_dm,
-                           dm_pad, (int)nao, (int)NX, (int)ndm);
-        NBX_LAUNCH_CHECK();
-        const int rc = nbx_jk_mx(ctx, NX, p0, p1, d_packed, dm_pad, ndm, jk_pad, d_work, nullptr, nullptr, nullptr);
-        if (rc != NBX_OK) return rc;
-        hipLaunchKernelGGL(s4_crop_square_kernel, dim3((unsigned)nbx_cdiv(tout, 256)), dim3(256), 0, ctx->stream,
-                           jk_pad, d_jk, (int)nao, (int)NX, (int)(1 + ndm));
-        NBX_LAUNCH_CHECK();
-        if (d_fock != nullptr) return nbx_fock_uhf(ctx, nao, d_hv, 3, nullptr, d_jk, d_fock, d_vhf);
-        return NBX_OK;
-    }
-    if (nbx_jk_m8_covers(nao)) return nbx_jk_m8(ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_dts);
-    if (const int64_t n8 = m8_padded(nao)) {
-        // (n8 > nao: as the n8 x n8 problem whose extra rows and columns are zero, like the jk_m4.hip branch below)
-        char* tail = static_cast<char*>(d_work) + nbx_jk_m8_worksize(n8, p0, p1, ndm);
-        double* dm_pad = reinterpret_cast<double*>(tail);
-        double* jk_pad = dm_pad + ndm * n8 * n8;
-        const int64_t tin = ndm * n8 * n8, tout = (1 + ndm) * nao * nao;
-        hipLaunchKernelGGL(s4_pad_square_kernel, dim3((unsigned)nbx_cdiv(tin, 256)), dim3(256), 0, ctx->stream, d_dm,
-                           dm_pad, (int)nao, (int)n8, (int)ndm);
-        NBX_LAUNCH_CHECK();
-        const int rc = nbx_jk_m8(ctx, n8, p0, p1, d_packed, dm_pad, ndm, jk_pad, d_work, nullptr, nullptr, nullptr, nullptr);
-        if (rc != NBX_OK) return rc;
-        hipLaunchKernelGGL(s4_crop_square_kernel, dim3((unsigned)nbx_cdiv(tout, 256)), dim3(256), 0, ctx->stream,
-                           jk_pad, d_jk, (int)nao, (int)n8, (int)(1 + ndm));
-        NBX_LAUNCH_CHECK();
-        if (d_fock != nullptr) return nbx_fock_uhf(ctx, nao, d_hv, 3, nullptr, d_jk, d_fock, d_vhf);
-        return NBX_OK;
-    }
-    if (nbx_jk_m4_covers(nao)) return nbx_jk_m4(ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_dts);
-    if (const int64_t n4 = m4_padded(nao)) {
-        // as the n4 x n4 problem whose extra rows and columns are zero (tiles with p >= nao are neither stored nor visited):
-        // D padded on the way in, J/K cropped on the way out, the Fock assembly its own launch
-        char* tail = static_cast<char*>(d_work) + nbx_jk_m4_worksize(n4, p0, p1, ndm);
-        double* dm_pad = reinterpret_cast<double*>(tail);
-        double* jk_pad = dm_pad + ndm * n4 * n4;
-        const int64_t tin = ndm * n4 * n4, tout = (1 + ndm) * nao * nao;
-        hipLaunchKernelGGL(s4_pad_square_kernel, dim3((unsigned)nbx_cdiv(tin, 256)), dim3(256), 0, ctx->stream, d_dm,
-                           dm_pad, (int)nao, (int)n4, (int)ndm);
-        NBX_LAUNCH_CHECK();
-        const int rc = nbx_jk_m4(ctx, n4, p0, p1, d_packed, dm_pad, ndm, jk_pad, d_work, nullptr, nullptr, nullptr, nullptr);
-        if (rc != NBX_OK) return rc;
-        hipLaunchKernelGGL(s4_crop_square_kernel, dim3((unsigned)nbx_cdiv(tout, 256)), dim3(256), 0, ctx->stream,
-                           jk_pad, d_jk, (int)nao, (int)n4, (int)(1 + ndm));
-        NBX_LAUNCH_CHECK();
-        if (d_fock != nullptr) return nbx_fock_uhf(ctx, nao, d_hv, 3, nullptr, d_jk, d_fock, d_vhf);
-        return NBX_OK;
-    }
-    if (nbx_jk_p8_covers(nao, p0, p1)) return nbx_jk_p8(ctx, nao, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_dts);
-    if (NPAD != nao) {
-        // Run as the NPAD x NPAD problem whose extra rows and columns are zero: the tiles (p, q) with
-        // p >= nao vanish (never stored, never visited); D is padded on the way in, J/K cropped on the
-        // way out.  The Fock assembly then is its own launch.
-        char* tail = static_cast<char*>(d_work) + s4_plan(NPAD, p0, p1 - p0, ndm).total;
-        double* dm_pad = reinterpret_cast<double*>(tail);
-        double* jk_pad = dm_pad + ndm * NPAD * NPAD;
-        const int64_t tin = ndm * NPAD * NPAD, tout = (1 + ndm) * nao * nao;
-        hipLaunchKernelGGL(s4_pad_square_kernel, dim3((unsigned)nbx_cdiv(tin, 256)), dim3(256), 0, ctx->stream, d_dm,
-                           dm_pad, (int)nao, (int)NPAD, (int)ndm);
-        NBX_LAUNCH_CHECK();
-        int rc = s4_jk_native(ctx, NPAD, p0, p1, d_packed, dm_pad, ndm, jk_pad, d_work, work_bytes, nullptr, nullptr,
-                              nullptr, nullptr);
-        if (rc != NBX_OK) return rc;
-        hipLaunchKernelGGL(s4_crop_square_kernel, dim3((unsigned)nbx_cdiv(tout, 256)), dim3(256), 0, ctx->stream,
-                           jk_pad, d_jk, (int)nao, (int)NPAD, (int)(1 + ndm));
-        NBX_LAUNCH_CHECK();
-        if (d_fock != nullptr) return nbx_fock_uhf(ctx, nao, d_hv, 3, nullptr, d_jk, d_fock, d_vhf);
-        return NBX_OK;
-    }
-    return s4_jk_native(ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, work_bytes, d_hv, d_fock, d_vhf, d_dts);
-}
-
-// the kernel proper, for a size it has an instance for (arguments checked by s4_jk)
-static int s4_jk_native(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm,
-                        int64_t ndm, double* d_jk, void* d_work, size_t work_bytes, const double* d_hv,
-                        double* d_fock, double* d_vhf, const double* d_dts) {
-    const int64_t np = p1 - p0, N = nao, n2 = N * N;
-    (void)work_bytes;
+// d_dts: NULL, or the Dtot' table of d_dm (left by nbx_huz_cycle_scalars_dts for this density): saves the preparation launch
+int nbx_jk_s4(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
+              double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_dts) {
+    const int64_t np = p1 - p0, n2 = N * N;
     const S4Plan pl = s4_plan(N, p0, np, ndm);
     char* base = static_cast<char*>(d_work);
     double* dtp = reinterpret_cast<double*>(base + pl.dtp_off);
@@ -656,7 +308,7 @@ static int s4_jk_native(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const
         const int rc = nbx_memset(ctx, d_jk, 0, (size_t)n2 * sizeof(double));
         if (rc != NBX_OK) return rc;
     }
-    if (d_dts != nullptr) {  // the caller's table (left by nbx_huz_cycle_scalars_dts for this density)
+    if (d_dts != nullptr) {
         dtp = const_cast<double*>(d_dts);
     } else {
         hipLaunchKernelGGL(s4_dtot_kernel, dim3((unsigned)nbx_cdiv(pl.NB * pl.NB * pl.lpt * 64, 256)), dim3(256), 0,
@@ -683,25 +335,13 @@ static int s4_jk_native(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const
         if (ndm == 2) NBX_S4_GO(2, NB_, LPT_, PD_, DT_, WV_);                                                              \
         else NBX_S4_GO(1, NB_, LPT_, PD_, DT_, WV_);                                                                       \
     } while (0)
-        if (pl.dma && !pl.s8) {
-            const int rcd = nbx_jk_s4d_launch(ctx, pl.dma, N, p0, np, ndm, pl.lpt, d_packed, d_dm, dtp, d_jk, k1, k2, t_begin,
-                                              t_end, pl.wgs, pl.L, pl.S);
-            if (rcd != NBX_OK) return rcd;
-        } else if (pl.s8) {
-            const int rc8 = nbx_jk_s8_launch(ctx, N, p0, np, ndm, d_packed, d_dm, dtp, d_jk, k1, k2, t_begin, t_end,
-                                             pl.wgs, pl.L, pl.S);
-            if (rc8 != NBX_OK) return rc8;
-        } else if (pl.NB == 2) {
+        if (pl.NB == 2) {
             if (pl.lpt == 2) NBX_S4_NDM(2, 2, 2, true, 2);
             else if (pl.lpt == 6) NBX_S4_NDM(2, 6, 2, true, 2);
             else NBX_S4_NDM(2, 10, 2, true, 1);
         } else {
             if (pl.lpt == 2) NBX_S4_NDM(4, 2, 4, true, 2);
-            else if (pl.lpt == 6) {
-                static const bool dt_stream = getenv("NBX_S4_DT_STREAM") != nullptr;  // probe: Dtot' re-read per chunk
-                if (dt_stream) NBX_S4_NDM(4, 6, 2, false, 2);
-                else NBX_S4_NDM(4, 6, 2, true, 2);
-            }
+            else if (pl.lpt == 6) NBX_S4_NDM(4, 6, 2, true, 2);
             else if (pl.lpt == 10) NBX_S4_NDM(4, 10, 2, true, 1);   // one workgroup per CU (LDS): 512 registers
             else NBX_S4_NDM(4, 17, 1, false, 1);
         }

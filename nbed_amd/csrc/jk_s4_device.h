@@ -1,11 +1,8 @@
-// Device pieces of the packed J/K kernels shared by jk_s4.hip (4-fold tiles) and jk_p8.hip (8-fold,
-// truncated tiles): the non-temporal 16-byte load, the inverse of the tile layout, and the walk of
-// one LDS-resident chunk.
+// Device pieces of the packed J/K kernel of jk_s4.hip (4-fold tiles): the non-temporal 16-byte load, the
+// inverse of the tile layout, and the walk of one LDS-resident chunk.
 #pragma once
 #include "jk_s4_layout.h"
 #include "nbx_common.h"
-
-int nbx_jk_s4_dtot(nbx_ctx* ctx, int64_t N, const double* d_dm, int64_t ndm, double* d_dts);  // jk_s4.hip
 
 namespace {
 

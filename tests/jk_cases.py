@@ -206,8 +206,58 @@ def packed_id(c) -> str:
     return f"{KERNEL_NAMES[c.kernel]}-{c.n}" + (f"as{c.run_as}" if c.run_as != c.n else "")
 
 
+# ------------------------------------------------------------------------------------------ the size queries
+# tests/golden/jk_packed_sizes.json (tests/golden/make_jk_packed_sizes.py, tests/test_host_jk_packed_sizes.py): what the
+# host-arithmetic queries of the packed J/K answer for every size, under the default and under these switch settings
+# (the last one is where jk_mx.hip takes 144 .. 148 although jk_m8.hip covers them)
+SIZE_SETTINGS = ["", *SWITCH_CASES, "NBX_JK_M4=0"]
+SIZE_RANGE = 421
+
+
+def size_slabs(n: int):
+    """The row ranges the byte counts are asked for: the whole tensor, then the slabs of equal_work_cuts."""
+    return [(0, n)] + equal_work_cuts(n)
+
+
+def packed_size_answers(lib) -> dict:
+    """Per query, one entry per n in range(SIZE_RANGE); packed_bytes / worksize: one number per slab of size_slabs(n)
+    (worksize: for ndm = 1, then for ndm = 2)."""
+    sizes = range(SIZE_RANGE)
+    routes = [route(lib, n) for n in sizes]
+    return {
+        "supported": [lib.nbx_jk_packed_supported(n) for n in sizes],
+        "fold": [lib.nbx_jk_packed_fold(n) for n in sizes],
+        "kernel": [k for k, _ in routes],
+        "run_as": [r for _, r in routes],
+        "dts_bytes": [lib.nbx_jk_dts_bytes(n) for n in sizes],
+        "packed_bytes": [[lib.nbx_eri_packed_bytes(n, p0, p1) for p0, p1 in size_slabs(n)] for n in sizes],
+        "worksize": [[lib.nbx_jk_packed_worksize(n, p0, p1, ndm) for ndm in (1, 2) for p0, p1 in size_slabs(n)]
+                     for n in sizes],
+    }
+
+
+def packed_size_answers_in_child(setting: str) -> dict:
+    """packed_size_answers of the built library in a fresh process under `setting` (the switches are read once per
+    process; host arithmetic only, no GPU)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    code = ("import json, sys; sys.path.insert(0, sys.argv[1]); import jk_cases as jc; from nbed_amd import _nbx; "
+            "print('SIZES', json.dumps(jc.packed_size_answers(_nbx.load_library())))")
+    tests = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONPATH=os.path.dirname(tests))
+    for name in ("NBX_JK_M8", "NBX_JK_M4", "NBX_JK_MX"):
+        env.pop(name, None)
+    env.update(item.split("=") for item in setting.split())
+    r = subprocess.run([sys.executable, "-c", code, tests], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return json.loads(r.stdout.rsplit("SIZES", 1)[1])
+
+
 # ------------------------------------------------------------------------------------------ operands
-Operands = namedtuple("Operands", "b dm hv e")
+Operands =namedtuple("Operands", "b dm hv e")
 
 
 def _sym_choice(rng, values, n):

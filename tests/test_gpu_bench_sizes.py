@@ -246,55 +246,6 @@ def test_fused_huzinaga_scf_bench_inputs_vs_oracle(be, eri148):
         assert abs(np.trace(d[x] @ s @ pr["D_env"][x] @ s)) < 1e-9
 
 
-def _experimental_build() -> bool:
-    """libnbx built with `make -C nbed_amd/csrc EXPERIMENTAL=1` (the J/K experiments of DESIGN.md section 9 linked in)."""
-    from nbed_amd import _nbx
-
-    return bool(_nbx.load_library().nbx_experimental())
-
-
-needs_experimental = pytest.mark.skipif("not _experimental_build()",
-                                        reason="the shipped libnbx.so holds no experiments: make EXPERIMENTAL=1")
-
-
-@needs_experimental
-def test_jk_eightfold_experimental_vs_c_oracle():
-    """csrc/jk_p8.hip (8-fold tiles; opt-in, NBX_JK_P8=1 is read once per process: a child process) at
-    N = 148 and 104 against oracle/c/jk_ref.c, the Fock epilogue included."""
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-
-    env = dict(os.environ, NBX_JK_P8="1")
-    out = subprocess.run([sys.executable, str(Path(__file__).with_name("_p8_worker.py"))], env=env, capture_output=True,
-                         text=True, timeout=600)
-    assert out.returncode == 0 and "P8 OK" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
-
-
-@needs_experimental
-@pytest.mark.parametrize("variant", ["1", "2", "3"])
-def test_jk_lds_dma_experimental_vs_c_oracle(variant):
-    """csrc/jk_s4d.hip (tiles streamed straight into LDS; opt-in) in a child process with
-    NBX_JK_DMA set: parity with the C oracle at the bench size; variants 1 and 2 keep the production kernel's
-    work distribution and give its numbers bit for bit (variant 3 runs three workgroups per CU: other partial
-    sums, other rounding)."""
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-
-    outs = {}
-    for v in (variant, "0") if variant != "3" else (variant,):
-        env = dict(os.environ, NBX_JK_DMA=v)
-        out = subprocess.run([sys.executable, str(Path(__file__).with_name("_s4d_worker.py"))], env=env,
-                             capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and "S4D OK" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
-        outs[v] = out.stdout.strip().splitlines()[-1].split(" ", 3)[3]
-    if variant != "3":
-        assert outs[variant] == outs["0"]
-
-
 @pytest.mark.parametrize("m4", ["1", "0"])
 def test_jk_packed_n148_both_kernels_vs_symmetric_kernel(m4):
     """N = 148 is served by csrc/jk_m4.hip (the walk on v_mfma_f64_4x4x4_4b_f64 over block-major tiles streamed into LDS by
