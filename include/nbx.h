@@ -723,6 +723,21 @@ int nbx_mu_cycle_fock_post(nbx_ctx* ctx, const nbx_huz_state* st, const double* 
 #define NBX_XC_PBEH 6
 #define NBX_XC_BLYP 7
 #define NBX_XC_B3LYP5 8
+/* nbx_xc_functional_rs: the semi-local part of a range-separated hybrid (what libxc evaluates behind dft.UKS.get_veff,
+ * nbed/driver.py:155-191, when xc_functional names one), nbx_xc_functional's arguments and outputs plus the range
+ * separation omega >= 0 (NBX_E_INVALID otherwise, and for every code but these two; nbx_xc_functional refuses them):
+ *   NBX_XC_CAM_B3LYP = 0.35 (Slater + B88) + 0.46 B88^sr(omega) + 0.81 LYP + 0.19 VWN5 (Yanai, Tew and Handy, Chem. Phys.
+ *     Lett. 393, 51 (2004): alpha = 0.19, beta = 0.46, omega = 0.33; exact part 0.19 K + 0.46 K_lr(omega), the caller's)
+ *   NBX_XC_LC_BLYP   = B88^sr(omega) + LYP (exact part K_lr(omega))
+ * B88^sr: the B88 exchange of a spin channel, Slater part and gradient correction together, times the attenuation
+ * factor F(a) of Iikura, Tsuneda, Yanai and Hirao (J. Chem. Phys. 115, 3540 (2001)), a = omega / (2 k_sigma),
+ * k_sigma = sqrt(9 pi / K_sigma) rho_sigma^(1/3) for e_sigma = -1/2 rho_sigma^(4/3) K_sigma; F by its closed form below
+ * a = 1/2 and by its series in 1 / a^2 from there on.                                          */
+#define NBX_XC_CAM_B3LYP 16
+#define NBX_XC_LC_BLYP 17
+int nbx_xc_functional_rs(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho, const double* d_grad,
+                         const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
+                         size_t work_bytes);
 int nbx_xc_rho(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao, const double* d_dm,
                double* d_rho, double* d_grad);
 size_t nbx_xc_functional_worksize(int64_t npts);
@@ -789,6 +804,16 @@ int nbx_threshold_scale(nbx_ctx* ctx, int64_t n, double tol, double scale, doubl
 int nbx_host_eri(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
                  const double* exps, const double* coefs, const double* sph, double cutoff, int nthreads,
                  double* out);
+/* The same tensor over the attenuated operator, (pq| erf(omega r12) / r12 |rs): the long-range integrals of a
+ * range-separated hybrid (mol.intor("int2e") under mol.with_range_coulomb(omega), what PySCF's get_veff asks for when
+ * xc_functional -- handed over untouched at nbed/driver.py:155-191 -- names one).  Per primitive quartet with
+ * alpha = p q / (p + q) it is the plain integral at alpha_w = alpha omega^2 / (alpha + omega^2), in the Boys argument
+ * and in the powers (-2 alpha_w)^n, times omega / sqrt(alpha + omega^2); nbx_host_eri is its omega = infinity case and
+ * runs the same code.  The quartets skipped are nbx_host_eri's: the Schwarz bounds of 1 / r12 bound the attenuated
+ * integrals too.  omega finite and > 0, else NBX_E_INVALID.                                                          */
+int nbx_host_eri_erf(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                     const double* exps, const double* coefs, const double* sph, double cutoff, double omega,
+                     int nthreads, double* out);
 /* Overlap, kinetic-energy and nuclear-attraction matrices (nao, nao) of the same shells, HOST memory:
  * intor("int1e_ovlp"), ("int1e_kin"), ("int1e_nuc") behind get_ovlp() / get_hcore() (nbed/driver.py:155-191).
  *   charges (natm), atom_xyz (natm, 3): the point charges of V (nuclei; Bohr)                      */
@@ -819,6 +844,13 @@ int nbx_host_dipole(int nshell, const int* ang, const int* nprim, const int* nfu
 #define NBX_ERI_CLASSES 25
 int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
                    const double* exps, const double* coefs, const double* sph, double cutoff, double* out_device);
+/* nbx_eri_device_erf: the tensor of nbx_host_eri_erf, (pq| erf(omega r12) / r12 |rs) (mol.with_range_coulomb(omega)
+ * around the intor("int2e") of nbed/driver.py:155-191), by the same class kernel: omega travels with the kernel's
+ * arguments, nbx_eri_device is the omega = infinity case.  Quartet lists, launches (nbx_eri_plan answers for every
+ * omega), storing rule, profiling and refusals as nbx_eri_device; omega finite and > 0, else NBX_E_INVALID.         */
+int nbx_eri_device_erf(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc,
+                       const double* centres, const double* exps, const double* coefs, const double* sph, double cutoff,
+                       double omega, double* out_device);
 int nbx_eri_class_ms(nbx_ctx* ctx, double* ms_out);
 /* Test support and launch geometry of nbx_eri_device -- the function its launcher asks, host arithmetic only (no
  * context, no GPU; the intor("int2e") call of nbed/driver.py:155-191 has no counterpart of it).  Per class

@@ -515,9 +515,10 @@ class HipBackend:
         return out
 
     # ------------------------------------------------------------------ AO integrals of a real molecule
-    def eri(self, basis, cutoff: float = 1e-16):
+    def eri(self, basis, cutoff: float = 1e-16, omega: float | None = None):
         """(pq|rs) of ``basis`` (``nbed_amd.integrals.Basis``, shells of l <= 2) as a device tensor (nao,)*4
-        (nbx_eri_device): zeroed and filled on this backend's stream, no host copy."""
+        (nbx_eri_device): zeroed and filled on this backend's stream, no host copy.  ``omega``: the tensor over
+        erf(omega r12) / r12 (nbx_eri_device_erf), same quartets, launches and storing rule."""
         from .integrals import _shell_arrays, max_ang
 
         if max_ang(basis) > 2:
@@ -526,8 +527,16 @@ class HipBackend:
         arrays = _shell_arrays(basis)
         out = self.empty((basis.nao,) * 4)
         ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-        self._call("nbx_eri_device", len(basis.shells), *(ptr(a) for a in arrays), float(cutoff), self._p(out))
+        if omega is None:
+            self._call("nbx_eri_device", len(basis.shells), *(ptr(a) for a in arrays), float(cutoff), self._p(out))
+        else:
+            self._call("nbx_eri_device_erf", len(basis.shells), *(ptr(a) for a in arrays), float(cutoff), float(omega),
+                       self._p(out))
         return out
+
+    def eri_device(self, basis, cutoff: float = 1e-16, omega: float | None = None):
+        """``eri`` under the name of its C entry point."""
+        return self.eri(basis, cutoff=cutoff, omega=omega)
 
     def _eri_shell_args(self, basis, what: str):
         from .integrals import _shell_arrays, max_ang
@@ -1183,6 +1192,17 @@ class HipBackend:
         work = self._workspace("xc_fn", nbytes)
         self._call("nbx_xc_functional", int(code), g, self._p(rho), self._p(grad), self._p(w), float(rho_floor), self._p(vr),
                    self._p(vec), self._p(sums), self._p(work), work.numel())
+        return vr, vec, sums
+
+    def xc_functional_rs(self, code: int, omega: float, rho, grad, w, rho_floor: float):
+        """``xc_functional`` for the semi-local part of a range-separated hybrid (nbx_xc_functional_rs: ``code`` from
+        ``_nbx.XC_RS_CODES``, ``omega`` the range separation of its short-range B88 exchange)."""
+        g = int(rho.shape[-1])
+        vr, vec, sums = self.empty((2, g)), self.empty((2, 3, g)), self.empty(2)
+        nbytes = int(self.lib.nbx_xc_functional_worksize(g))
+        work = self._workspace("xc_fn", nbytes)
+        self._call("nbx_xc_functional_rs", int(code), float(omega), g, self._p(rho), self._p(grad), self._p(w),
+                   float(rho_floor), self._p(vr), self._p(vec), self._p(sums), self._p(work), work.numel())
         return vr, vec, sums
 
     def xc_vmat(self, ao, dao, vr, vec):

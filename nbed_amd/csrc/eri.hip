@@ -122,7 +122,9 @@ __global__ __launch_bounds__(ERI_BLOCK) void eri_class_kernel(EriArgs a, const u
             for (int j = 0; j < cd.nprim; ++j) {
                 const double* qq = a.prim + 4 * (cd.prim_off + j);
                 const double q = qq[0];
-                const double alpha = p * q / (p + q);
+                // erf(omega r12) / r12: p + q + p q / omega^2 in the place of p + q (Engine::inv_w2); p + q itself for 1 / r12
+                const double pq_w = p + q + p * q * a.inv_w2;
+                const double alpha = p * q / pq_w;
                 const double x = px - qq[1], y = py - qq[2], z = pz - qq[3];
                 // hermite_r: F_n(alpha |PQ|^2), then R^n_tuv for n = L .. 0, each pass from the one before
                 double f[L + 1], pw[L + 1];
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(ERI_BLOCK) void eri_class_kernel(EriArgs a, const u
                     double* s = cur; cur = old; old = s;
                 }
                 const double* rb = old;  // the last pass
-                const double pref = a.pref0 / (p * q * sqrt(p + q));
+                const double pref = a.pref0 / (p * q * sqrt(pq_w));
                 const double* hcd = a.h + cd.h_off + size_t(j) * ncd * NHCD;
                 // w[c][k_ab] = pref sum_k_cd (-1)^(tau+nu+phi) H_cd[c][k_cd] R[k_ab + k_cd]
                 for (int idx = lane; idx < ncd * NHAB; idx += ERI_BLOCK) {
@@ -303,20 +305,22 @@ struct Plan {
 
 // Shells, index tables and pair data; NBX_E_INVALID where nbx_host_eri refuses the shells, and for l > 2.
 int make_engine(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres, const double* exps,
-                const double* coefs, const double* sph, double cutoff, Engine& eng) {
+                const double* coefs, const double* sph, double cutoff, double inv_w2, Engine& eng) {
     if (nshell <= 0 || !ang || !nprim || !nfunc || !centres || !exps || !coefs || !sph) return NBX_E_INVALID;
     eng.cutoff = cutoff;
+    eng.inv_w2 = inv_w2;
     if (engine_shells(eng, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, DEV_LMAX) != NBX_OK) return NBX_E_INVALID;
     engine_tables(eng);
     engine_pairs(eng, std::min(pool_size(0), 16));
     return NBX_OK;
 }
 
-// What nbx_eri_plan and nbx_eri_device start from: the engine and the canonical quartets of the dense tensor.
+// What nbx_eri_plan and nbx_eri_device start from: the engine and the canonical quartets of the dense tensor.  The lists
+// do not depend on inv_w2 (the Schwarz bounds are those of 1 / r12), so nbx_eri_plan answers for every omega.
 int make_plan(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres, const double* exps,
-              const double* coefs, const double* sph, double cutoff, bool want_lists, Plan& pl) {
+              const double* coefs, const double* sph, double cutoff, double inv_w2, bool want_lists, Plan& pl) {
     Engine& eng = pl.eng;
-    if (make_engine(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, eng) != NBX_OK) return NBX_E_INVALID;
+    if (make_engine(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, inv_w2, eng) != NBX_OK) return NBX_E_INVALID;
     const int64_t npair = int64_t(eng.pairs.size());
     auto each = [&](auto&& fn) {
         for (int64_t ij = npair - 1; ij >= 0; --ij) {
@@ -408,6 +412,7 @@ EriArgs args_of(const char* d_img, const Image& im, const Engine& eng, double* o
     args.tabs = reinterpret_cast<const int*>(d_img + im.o_tabs);
     args.out = out;
     args.pref0 = 2.0 * std::pow(M_PI, 2.5);
+    args.inv_w2 = eng.inv_w2;
     args.nao = eng.nao;
     return args;
 }
@@ -430,7 +435,7 @@ extern "C" int nbx_eri_plan(int nshell, const int* ang, const int* nprim, const 
                             int* lds_bytes_out, int* block_out, int64_t* grid_out) {
     if (!counts_out || !lds_bytes_out || !block_out || !grid_out) return NBX_E_INVALID;
     Plan pl;
-    const int rc = make_plan(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, false, pl);
+    const int rc = make_plan(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, 0.0, false, pl);
     if (rc != NBX_OK) return rc;
     for (int lab = 0; lab < NLP; ++lab)
         for (int lcd = 0; lcd < NLP; ++lcd) {
@@ -443,13 +448,15 @@ extern "C" int nbx_eri_plan(int nshell, const int* ang, const int* nprim, const 
     return NBX_OK;
 }
 
-extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc,
-                              const double* centres, const double* exps, const double* coefs, const double* sph,
-                              double cutoff, double* out_device) {
+namespace {
+
+// nbx_eri_device (inv_w2 = 0) and nbx_eri_device_erf (inv_w2 = 1 / omega^2)
+int eri_device(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+               const double* exps, const double* coefs, const double* sph, double cutoff, double inv_w2, double* out_device) {
     NBX_CHECK_ARG(ctx != nullptr);
     NBX_CHECK_ARG(out_device != nullptr);
     Plan pl;
-    if (make_plan(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, true, pl) != NBX_OK) {
+    if (make_plan(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, inv_w2, true, pl) != NBX_OK) {
         nbx_set_error("nbx_eri_device: invalid shells (angular momentum 0 .. %d, nfunc = 2l+1 or (l+1)(l+2)/2)", DEV_LMAX);
         return NBX_E_INVALID;
     }
@@ -514,12 +521,30 @@ extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const in
     return rc;
 }
 
+}  // namespace
+
+extern "C" int nbx_eri_device(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc,
+                              const double* centres, const double* exps, const double* coefs, const double* sph,
+                              double cutoff, double* out_device) {
+    return eri_device(ctx, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, 0.0, out_device);
+}
+
+extern "C" int nbx_eri_device_erf(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc,
+                                  const double* centres, const double* exps, const double* coefs, const double* sph,
+                                  double cutoff, double omega, double* out_device) {
+    if (!(omega > 0.0) || !std::isfinite(omega)) {
+        nbx_set_error("nbx_eri_device_erf: omega = %g; a finite omega > 0 is required", omega);
+        return NBX_E_INVALID;
+    }
+    return eri_device(ctx, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, 1.0 / (omega * omega), out_device);
+}
+
 // ------------------------------------------------------------------------------------------ diagonal and columns
 namespace nbx_eri {
 
 int session_open(nbx_ctx* ctx, int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
                  const double* exps, const double* coefs, const double* sph, double cutoff, Session& s) {
-    if (make_engine(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, s.eng) != NBX_OK) return NBX_E_INVALID;
+    if (make_engine(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, 0.0, s.eng) != NBX_OK) return NBX_E_INVALID;
     s.stream = ctx->stream;
     s.cutoff = cutoff;
     Image im;

@@ -70,6 +70,7 @@ struct EriArgs {
     const int* tabs;      // NLP x NH_MAX packed (t, u, v) in HermIndex order, then NR_MAX sorted by t + u + v
     double* out;          // the sink's buffer: (nao)^4 tensor, (nao, nao) diagonal or (ncols, nao, nao) columns
     double pref0;         // 2 pi^(5/2)
+    double inv_w2;        // Engine::inv_w2: 1 / omega^2 of erf(omega r12) / r12, 0 for 1 / r12
     int nao;
 };
 

@@ -21,12 +21,15 @@
 
 using namespace nbx_md;
 
-extern "C" int nbx_host_eri(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
-                            const double* exps, const double* coefs, const double* sph, double cutoff, int nthreads,
-                            double* out) {
+namespace {
+
+// (pq| erf(omega r12) / r12 |rs) with inv_w2 = 1 / omega^2; 0: the plain tensor
+int host_eri(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres, const double* exps,
+             const double* coefs, const double* sph, double cutoff, double inv_w2, int nthreads, double* out) {
     if (nshell <= 0 || !ang || !nprim || !nfunc || !centres || !exps || !coefs || !sph || !out) return NBX_E_INVALID;
     Engine eng;
     eng.cutoff = cutoff;
+    eng.inv_w2 = inv_w2;
     if (engine_shells(eng, nshell, ang, nprim, nfunc, centres, exps, coefs, sph, LMAX) != NBX_OK) return NBX_E_INVALID;
     engine_tables(eng);
 
@@ -94,6 +97,21 @@ extern "C" int nbx_host_eri(int nshell, const int* ang, const int* nprim, const 
         }
     });
     return NBX_OK;
+}
+
+}  // namespace
+
+extern "C" int nbx_host_eri(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                            const double* exps, const double* coefs, const double* sph, double cutoff, int nthreads,
+                            double* out) {
+    return host_eri(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, 0.0, nthreads, out);
+}
+
+extern "C" int nbx_host_eri_erf(int nshell, const int* ang, const int* nprim, const int* nfunc, const double* centres,
+                                const double* exps, const double* coefs, const double* sph, double cutoff, double omega,
+                                int nthreads, double* out) {
+    if (!(omega > 0.0) || !std::isfinite(omega)) return NBX_E_INVALID;
+    return host_eri(nshell, ang, nprim, nfunc, centres, exps, coefs, sph, cutoff, 1.0 / (omega * omega), nthreads, out);
 }
 
 // ------------------------------------------------------------------------------------------------------

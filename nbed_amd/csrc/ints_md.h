@@ -215,6 +215,12 @@ struct Engine {
     BoysTable boys;
     int nao = 0;
     double cutoff = 0.0;
+    // 1 / omega^2 of the operator erf(omega r12) / r12; 0 is 1 / r12 (omega = infinity).  Per primitive quartet the
+    // attenuated integral is the plain one at alpha_w = alpha / (1 + alpha / omega^2) times (1 + alpha / omega^2)^(-1/2)
+    // (DESIGN.md section 17).  Both are had by putting p + q + p q / omega^2 where the plain formulas have p + q:
+    // alpha_w = p q / that, and the prefactor's sqrt(p + q) becomes its root.  One multiply-add more per primitive
+    // quartet, and with 0 the sum is p + q itself: the plain arithmetic is unchanged bit for bit.
+    double inv_w2 = 0.0;
 
     // Cartesian block (nab x ncd) of the quartet (pairs ab, cd)
     void quartet_cart(const Pair& ab, const Pair& cd, double* blk, double* rbuf, double* rtmp, double* w) const {
@@ -227,9 +233,10 @@ struct Engine {
             const double* hab = &ab.h[size_t(i) * nab * nhab];
             for (int j = 0; j < cd.nprim; ++j) {
                 const double q = cd.p[j];
-                const double alpha = p * q / (p + q);
+                const double pq_w = p + q + p * q * inv_w2;  // (p + q) (1 + alpha / omega^2); p + q exactly for 1 / r12
+                const double alpha = p * q / pq_w;
                 hermite_r(l, alpha, ab.px[i] - cd.px[j], ab.py[i] - cd.py[j], ab.pz[i] - cd.pz[j], boys, rbuf, rtmp);
-                const double pref = 2.0 * std::pow(M_PI, 2.5) / (p * q * std::sqrt(p + q));
+                const double pref = 2.0 * std::pow(M_PI, 2.5) / (p * q * std::sqrt(pq_w));
                 const double* hcd = &cd.h[size_t(j) * ncd * nhcd];
                 // w[c][k_ab] = sum_k_cd (-1)^(tau+nu+phi) H_cd[c][k_cd] R[k_ab + k_cd]
                 for (int c = 0; c < ncd; ++c) {
@@ -338,12 +345,17 @@ inline void engine_tables(Engine& eng) {
             eng.sgn[l][k] = ((eng.hidx[l].tuv[k][0] + eng.hidx[l].tuv[k][1] + eng.hidx[l].tuv[k][2]) & 1) ? -1.0 : 1.0;
 }
 
-// pair data and Schwarz bounds sqrt(max (ab|ab)) of every shell pair ia >= ib, over nthreads threads
+// pair data and Schwarz bounds sqrt(max (ab|ab)) of every shell pair ia >= ib, over nthreads threads.  The bounds are
+// those of 1 / r12 whatever eng.inv_w2 is set to afterwards: (ab|ab)_omega <= (ab|ab) (the Fourier transform of
+// erf(omega r) / r is that of 1 / r times exp(-k^2 / 4 omega^2) <= 1), so they bound the attenuated quartets too and
+// every omega runs the same quartet lists.
 inline void engine_pairs(Engine& eng, int nthreads) {
     const int nshell = int(eng.shells.size());
     const int64_t npair = int64_t(nshell) * (nshell + 1) / 2;
     eng.pairs.resize(npair);
     const double prim_cutoff = eng.cutoff * 1e-4;
+    const double inv_w2 = eng.inv_w2;
+    eng.inv_w2 = 0.0;
     std::atomic<int64_t> next{0};
     run_pool(nthreads, [&] {
         std::vector<double> blk(100 * 100), w(100 * 84), rbuf(NCUBE * NCUBE * NCUBE), rtmp(NCUBE * NCUBE * NCUBE);
@@ -363,6 +375,7 @@ inline void engine_pairs(Engine& eng, int nthreads) {
             pr.schwarz = std::sqrt(mx);
         }
     });
+    eng.inv_w2 = inv_w2;
 }
 
 // the test both engines apply to a canonical quartet (kl <= ij)

@@ -156,6 +156,68 @@ __device__ __forceinline__ void xc_b88(double s, double r, double sg, double& e,
     vs += s * (-beta * gpx / (2.0 * r43));
 }
 
+// The attenuation factor of Iikura, Tsuneda, Yanai and Hirao (J. Chem. Phys. 115, 3540 (2001)),
+//   F(a) = 1 - (8/3) a [sqrt(pi) erf(1 / (2a)) + 2a (b - c)],  b = exp(-1 / (4 a^2)) - 1,  c = 2 a^2 b + 1/2,
+// and P = F + a F' / 2, the combination both derivatives of the short-range exchange need:
+//   a F' = -(8/3) a [sqrt(pi) erf(1 / (2a)) + 2 a b - 16 a^3 b - 4 a].
+// The bracket tends to 3/8 while F falls like 1 / (36 a^2): in float64 the closed form loses 36 a^4 ulp.  With
+// t = 1 / (4 a^2) every term is a power series in t and the sum is F = sum_{m >= 1} c_m t^m,
+//   c_m = -(8/3) (-1)^m [1 / (m! (2m + 1)) - 1 / (2 (m + 1)!) - 1 / (4 (m + 2)!)]   (c_1 = 1/9: F -> 1 / (36 a^2)),
+// a F' = -2 sum m c_m t^m, so P = sum (1 - m) c_m t^m starts at t^2: formed as F + a F' / 2 it would lose 27 a^2 ulp more,
+// summed term by term it loses none.  Sixteen terms from a = 1/2 on (t <= 1), the closed form below: measured against
+// 80 digits the series is good to 3e-16 relative from the switch on and the closed form to 1.3e-15 below it (DESIGN.md
+// section 17; at a = 0.4 the series is at 1e-13, at a = 0.7 the closed form at 1.2e-14).  a < 1e-60 (omega = 0):
+// F = 1 - (8/3) sqrt(pi) a, where 1 / a^4 would overflow in a derivative.
+__device__ __forceinline__ void xc_ityh(double a, double& f, double& p) {
+    constexpr double C[16] = {1.0 / 9.0, -1.0 / 60.0, 1.0 / 420.0, -1.0 / 3240.0, 1.0 / 27720.0, -1.0 / 262080.0, 1.0 / 2721600.0,
+                              -1.0 / 30844800.0, 1.0 / 379209600.0, -1.0 / 5029516800.0, 1.0 / 71610739200.0,
+                              -1.0 / 1089728640000.0, 1.0 / 17653603968000.0, -1.0 / 303380453376000.0,
+                              1.0 / 5513155135488000.0, -1.0 / 105639166144512000.0};
+    const double sqrt_pi = 1.7724538509055159;
+    if (a >= 0.5) {
+        const double t = 0.25 / (a * a);
+        double sf = C[15], sp = 15.0 * C[15];
+#pragma unroll
+        for (int m = 15; m >= 1; --m) {
+            sf = fma(sf, t, C[m - 1]);
+            sp = fma(sp, t, (m - 1) * C[m - 1]);
+        }
+        f = t * sf;
+        p = -t * sp;
+    } else if (a < 1.0e-60) {
+        f = 1.0 - (8.0 / 3.0) * sqrt_pi * a;
+        p = 1.0 - 4.0 * sqrt_pi * a;
+    } else {
+        const double b = expm1(-0.25 / (a * a)), er = sqrt_pi * erf(0.5 / a);
+        const double c = fma(2.0 * a * a, b, 0.5);
+        f = 1.0 - (8.0 / 3.0) * a * (er + 2.0 * a * (b - c));
+        p = f - (4.0 / 3.0) * a * (er + 2.0 * a * b - 16.0 * a * a * a * b - 4.0 * a);
+    }
+}
+
+// Short-range B88 exchange of one spin channel in the ITYH scheme: with the whole B88 exchange e = -rho^(4/3) G(x),
+// G = cx + beta g(x) (Slater + Becke's correction, xc_b88's g), written as -1/2 rho^(4/3) K, K = 2 G, the local Fermi
+// wave vector is k = sqrt(9 pi / K) rho^(1/3) ((6 pi^2 rho)^(1/3) for G = cx), a = omega / (2 k) and e_sr = e F(a).
+// With da/drho = -a (1 + 2 x G'/G) / (3 rho), da/dsigma = a G' / (2 G) dx/dsigma and P = F + a F' / 2:
+//   de/drho   = rho^(1/3) [G (-2 F + (2/3) P) + (4/3) x G' P],   x G' = beta x^2 (g'/x)
+//   de/dsigma = -beta (g'/x) P / (2 rho^(4/3))
+__device__ __forceinline__ void xc_b88_sr(double s, double omega, double r, double sg, double& e, double& vr, double& vs) {
+    const double beta = 0.0042, cx = 0.9305257363491002;
+    const double r13 = cbrt(r), r43 = r13 * r;
+    const double x = sqrt(sg) / r43;
+    const double ash = asinh(x);
+    const double den = fma(6.0 * beta * x, ash, 1.0);
+    const double g = x * x / den;
+    const double gpx = (2.0 * den - 6.0 * beta * x * (ash + x / sqrt(fma(x, x, 1.0)))) / (den * den);
+    const double G = fma(beta, g, cx), xG1 = beta * x * x * gpx;
+    const double a = omega * sqrt(2.0 * G) / (10.634723105433095 * r13);  // 6 sqrt(pi)
+    double f, p;
+    xc_ityh(a, f, p);
+    e += s * (-r43 * G * f);
+    vr += s * r13 * (G * ((2.0 / 3.0) * p - 2.0 * f) + (4.0 / 3.0) * xG1 * p);
+    vs += s * (-beta * gpx * p / (2.0 * r43));
+}
+
 // VWN's interpolation formula eps(x), x = sqrt(rs), and d eps / dx
 __device__ __forceinline__ void xc_vwn_fit(double x, double a, double x0, double b, double c, double& e, double& de) {
     const double q = sqrt(4.0 * c - b * b);
@@ -370,8 +432,9 @@ __device__ __forceinline__ void xc_pbe_c(double s, double ra, double rb, double 
 
 constexpr int XC_FN_THREADS = 256;
 
-// CODE: NBX_XC_SLATER / _LDA_VWN_RPA / _LDA_VWN5 / _B3LYP / _LDA_PW_MOD / _PBE / _PBEH / _BLYP / _B3LYP5 (the semi-local
-// part; the exact-exchange fraction is the caller's), one instantiation each: a kernel holding every branch would
+// CODE: NBX_XC_SLATER / _LDA_VWN_RPA / _LDA_VWN5 / _B3LYP / _LDA_PW_MOD / _PBE / _PBEH / _BLYP / _B3LYP5, and the
+// range-separated NBX_XC_CAM_B3LYP / _LC_BLYP of nbx_xc_functional_rs, which alone read `omega` (the semi-local
+// part; the exact-exchange fractions are the caller's), one instantiation each: a kernel holding every branch would
 // charge the registers of PBE correlation to the LDA codes.  Conventions of nbed_amd.xc.XCProvider.__call__ (the torch
 // expression this kernel replaces): densities clamped from below at rho_floor / 2, sigma_aa and sigma_bb lifted by
 // 1e-40, points with rho_a + rho_b <= rho_floor dropped; outputs carry the quadrature weights:
@@ -382,8 +445,8 @@ template <int CODE>
 __global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_kernel(int64_t npts, const double* __restrict__ rho,
                                                                       const double* __restrict__ grad,
                                                                       const double* __restrict__ w, double rho_floor,
-                                                                      double* __restrict__ vr, double* __restrict__ vec,
-                                                                      double* __restrict__ part) {
+                                                                      double omega, double* __restrict__ vr,
+                                                                      double* __restrict__ vec, double* __restrict__ part) {
     __shared__ double red[17];
     const int64_t g = (int64_t)blockIdx.x * XC_FN_THREADS + threadIdx.x;
     double e_w = 0.0, n_w = 0.0;
@@ -420,6 +483,18 @@ __global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_kernel(int64_t np
             xc_pbe_x(ax, ra, saa, o.e, o.va, o.vaa);
             xc_pbe_x(ax, rb, sbb, o.e, o.vb, o.vbb);
             xc_pbe_c(1.0, ra, rb, saa, sab, sbb, o);
+        } else if (CODE == NBX_XC_CAM_B3LYP) {  // (1 - 0.19 - 0.46) B88 + 0.46 B88^sr(omega) + 0.81 LYP + 0.19 VWN5
+            xc_slater(0.35, ra, rb, o);
+            xc_b88(0.35, ra, saa, o.e, o.va, o.vaa);
+            xc_b88(0.35, rb, sbb, o.e, o.vb, o.vbb);
+            xc_b88_sr(0.46, omega, ra, saa, o.e, o.va, o.vaa);
+            xc_b88_sr(0.46, omega, rb, sbb, o.e, o.vb, o.vbb);
+            xc_vwn<false>(0.19, ra, rb, o);
+            xc_lyp(0.81, ra, rb, saa, sab, sbb, o);
+        } else if (CODE == NBX_XC_LC_BLYP) {  // B88^sr(omega) + LYP
+            xc_b88_sr(1.0, omega, ra, saa, o.e, o.va, o.vaa);
+            xc_b88_sr(1.0, omega, rb, sbb, o.e, o.vb, o.vbb);
+            xc_lyp(1.0, ra, rb, saa, sab, sbb, o);
         } else {  // BLYP
             xc_slater(1.0, ra, rb, o);
             xc_b88(1.0, ra, saa, o.e, o.va, o.vaa);
@@ -609,11 +684,13 @@ extern "C" size_t nbx_xc_functional_worksize(int64_t npts) {
     return npts <= 0 ? 256 : xc_align256((size_t)(2 * nbx_cdiv(npts, XC_FN_THREADS)) * sizeof(double));
 }
 
-extern "C" int nbx_xc_functional(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
-                                 const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
-                                 size_t work_bytes) {
+namespace {
+
+// nbx_xc_functional (codes 0 .. 8, omega unused) and nbx_xc_functional_rs (codes from 16 on), arguments checked
+int xc_functional_launch(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho, const double* d_grad,
+                         const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
+                         size_t work_bytes) {
     NBX_CHECK_ARG(ctx && d_rho && d_grad && d_w && d_vr && d_vec && d_sums && d_work && npts >= 0);
-    NBX_CHECK_ARG(code >= NBX_XC_SLATER && code <= NBX_XC_B3LYP5);
     NBX_CHECK_ARG(rho_floor > 0.0 && work_bytes >= nbx_xc_functional_worksize(npts));
     if (npts == 0) return nbx_memset(ctx, d_sums, 0, 2 * sizeof(double));
     const int64_t nblk = nbx_cdiv(npts, XC_FN_THREADS);
@@ -622,7 +699,7 @@ extern "C" int nbx_xc_functional(nbx_ctx* ctx, int code, int64_t npts, const dou
 #define NBX_XC_FN(CODE_)                                                                                                  \
     case CODE_:                                                                                                           \
         hipLaunchKernelGGL(xc_functional_kernel<CODE_>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,  \
-                           d_rho, d_grad, d_w, rho_floor, d_vr, d_vec, part);                                             \
+                           d_rho, d_grad, d_w, rho_floor, omega, d_vr, d_vec, part);                                      \
         break
     switch (code) {
         NBX_XC_FN(NBX_XC_SLATER);
@@ -633,13 +710,32 @@ extern "C" int nbx_xc_functional(nbx_ctx* ctx, int code, int64_t npts, const dou
         NBX_XC_FN(NBX_XC_PBE);
         NBX_XC_FN(NBX_XC_PBEH);
         NBX_XC_FN(NBX_XC_BLYP);
-        default: NBX_XC_FN(NBX_XC_B3LYP5);
+        NBX_XC_FN(NBX_XC_B3LYP5);
+        NBX_XC_FN(NBX_XC_CAM_B3LYP);
+        default: NBX_XC_FN(NBX_XC_LC_BLYP);
     }
 #undef NBX_XC_FN
     NBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(xc_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, (int)nblk, part, d_sums);
     NBX_LAUNCH_CHECK();
     return NBX_OK;
+}
+
+}  // namespace
+
+extern "C" int nbx_xc_functional(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
+                                 const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
+                                 size_t work_bytes) {
+    NBX_CHECK_ARG(code >= NBX_XC_SLATER && code <= NBX_XC_B3LYP5);
+    return xc_functional_launch(ctx, code, 0.0, npts, d_rho, d_grad, d_w, rho_floor, d_vr, d_vec, d_sums, d_work, work_bytes);
+}
+
+extern "C" int nbx_xc_functional_rs(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho,
+                                    const double* d_grad, const double* d_w, double rho_floor, double* d_vr, double* d_vec,
+                                    double* d_sums, void* d_work, size_t work_bytes) {
+    NBX_CHECK_ARG(code == NBX_XC_CAM_B3LYP || code == NBX_XC_LC_BLYP);
+    NBX_CHECK_ARG(omega >= 0.0 && omega < 1.0e150);  // (finite; 0 is the plain B88: F(0) = 1)
+    return xc_functional_launch(ctx, code, omega, npts, d_rho, d_grad, d_w, rho_floor, d_vr, d_vec, d_sums, d_work, work_bytes);
 }
 
 extern "C" size_t nbx_xc_vmat_worksize(int64_t npts, int64_t nao) {

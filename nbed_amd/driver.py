@@ -214,7 +214,8 @@ class BuiltinHFProvider:
 
         from . import xc as xcmod
 
-        return (str(config.xc_functional).lower().replace(" ", "") in xcmod.HYBRID_FRACTION
+        name = str(config.xc_functional).lower().replace(" ", "")
+        return ((name in xcmod.HYBRID_FRACTION or name in xcmod.RSH_PARAMETERS)
                 and integrals.supports(config.geometry, str(config.basis)))
 
     def _integrals(self, config: NbedConfig):
@@ -308,6 +309,38 @@ class BuiltinHFProvider:
         if slot["donor"] is not None:
             out["eri_packed"] = slot["donor"].eri_packed_device()
         return out
+
+    def _refuse_rsh_on_a_factor(self, xc_functional: str):
+        from . import xc as xcmod
+
+        if self.eri_engine == "cholesky" and str(xc_functional).lower().replace(" ", "") in xcmod.RSH_PARAMETERS:
+            raise NbedDriverError(f"eri_engine='cholesky' with xc_functional={str(xc_functional)!r}: the long-range exchange of "
+                                  "a range-separated hybrid needs the dense attenuated tensor, which has no Cholesky route "
+                                  "(use 'auto', 'host' or 'device')")
+
+    def _eri_lr_kwargs(self, config: NbedConfig, xc_functional: str, backend) -> dict:
+        """``omega=``, ``alpha=``, ``beta=``, ``eri_lr=`` of a Kohn-Sham object: for a range-separated hybrid the tensor over
+        erf(omega r12) / r12, built once per (backend, molecule, omega) by the engine that builds the plain one
+        (``eri_engine`` auto | host | device); nothing for any other functional."""
+        from . import integrals
+        from . import xc as xcmod
+        from .backend import get_backend
+
+        omega, alpha, beta = xcmod.rsh_parameters(xc_functional)
+        if beta == 0.0:
+            return {}
+        self._refuse_rsh_on_a_factor(xc_functional)
+        be = backend if backend is not None else (self._be if self._be is not None else get_backend())
+        key = ("eri_lr", id(be), float(omega), config.geometry, str(config.basis).lower(), str(config.unit))
+        if key not in self._cache:
+            ints = self._integrals(config)
+            if self._eri_route(config) == "device":
+                eri_lr = be.eri(ints["basis"], omega=omega)
+            else:
+                basis = integrals.Basis(integrals.parse_geometry(config.geometry, str(config.unit)), str(config.basis))
+                eri_lr = be.asarray(integrals.two_electron_native(basis, omega=omega))
+            self._cache[key] = {"eri_lr": eri_lr, "be": be}
+        return {"omega": omega, "alpha": alpha, "beta": beta, "eri_lr": self._cache[key]["eri_lr"]}
 
     def _adopt(self, config: NbedConfig, obj):
         """Remember the first SCF object of a molecule as the owner of the packed copies."""
@@ -438,11 +471,12 @@ class BuiltinHFProvider:
         from . import xc as xcmod
         from .scf import GpuUKS
 
+        lr = self._eri_lr_kwargs(config, xc_functional, backend)  # (first: it refuses what has no attenuated tensor)
         ints = self._integrals(config)
         return self._adopt(config, GpuUKS(mol, ints["S"], ints["hcore"] if hcore is None else hcore, xc=str(xc_functional),
                                           hyb=xcmod.hybrid_fraction(xc_functional),
                                           xc_provider=self._xc_provider(config, xc_functional),
-                                          **self._eri_kwargs(config, backend)))
+                                          **self._eri_kwargs(config, backend), **lr))
 
     def global_ks(self, config: NbedConfig, run_qmmm: bool = False):
         """Converged global Kohn-Sham object (nbed/driver.py:155-191).  With ``run_qmmm`` it is built on hcore + V_mm and
@@ -452,8 +486,10 @@ class BuiltinHFProvider:
         if not self.supports(config):
             from . import xc as xcmod
 
-            raise NbedDriverError(f"BuiltinHFProvider covers xc_functional in {sorted(xcmod.HYBRID_FRACTION)} ('pbeh' / "
+            raise NbedDriverError(f"BuiltinHFProvider covers xc_functional in "
+                                  f"{sorted(xcmod.HYBRID_FRACTION) + sorted(xcmod.RSH_PARAMETERS)} ('pbeh' / "
                                   "'pbe1pbe' is the functional also called PBE0), H/C/N/O in STO-3G, 6-31G(*), cc-pVDZ")
+        self._refuse_rsh_on_a_factor(config.xc_functional)
         hcore, energy_nuc = self._with_mm(config, run_qmmm, self._be)
         if str(config.xc_functional).lower() != "hf":
             ks = self._uks(config, self.build_mol(config), config.xc_functional, self._be, hcore=hcore)

@@ -507,10 +507,21 @@ def molecule_dipole(xyz: str, basis: str = "sto-3g", unit: str = "angstrom", car
     return dipole_native(bs) if engine == "native" else dipole(bs)
 
 
-def two_electron_native(basis: Basis, nthreads: int = 0, cutoff: float = 1e-16) -> np.ndarray:
+def _check_omega(omega) -> float | None:
+    """``omega`` of erf(omega r12) / r12 as a float; None (1 / r12) stays None."""
+    if omega is None:
+        return None
+    omega = float(omega)
+    if not (omega > 0.0 and math.isfinite(omega)):
+        raise ValueError(f"omega = {omega}: the attenuated operator erf(omega r12) / r12 needs a finite omega > 0")
+    return omega
+
+
+def two_electron_native(basis: Basis, nthreads: int = 0, cutoff: float = 1e-16, omega: float | None = None) -> np.ndarray:
     """(pq|rs) from libnbx's host engine (``nbx_host_eri``, csrc/ints_host.cpp: the same McMurchie-Davidson
     scheme in C++ over a thread pool) -- what makes a 148-function molecule practical.  Raises if libnbx.so
-    is not built; ``two_electron`` above is the numpy engine it is tested against."""
+    is not built; ``two_electron`` above is the numpy engine it is tested against.  ``omega``: the tensor over
+    erf(omega r12) / r12 instead (``nbx_host_eri_erf``), the long-range integrals of a range-separated hybrid."""
     import ctypes
 
     from . import _nbx
@@ -526,8 +537,12 @@ def two_electron_native(basis: Basis, nthreads: int = 0, cutoff: float = 1e-16) 
     sph = np.concatenate([np.ascontiguousarray(s.sph, dtype=np.float64).ravel() for s in sh])
     out = np.empty((basis.nao,) * 4)
     ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    _nbx.check(lib, lib.nbx_host_eri(len(sh), ptr(ang), ptr(nprim), ptr(nfunc), ptr(centres), ptr(exps), ptr(coefs),
-                                     ptr(sph), float(cutoff), int(nthreads), ptr(out)))
+    shells = (len(sh), ptr(ang), ptr(nprim), ptr(nfunc), ptr(centres), ptr(exps), ptr(coefs), ptr(sph))
+    omega = _check_omega(omega)
+    if omega is None:
+        _nbx.check(lib, lib.nbx_host_eri(*shells, float(cutoff), int(nthreads), ptr(out)))
+    else:
+        _nbx.check(lib, lib.nbx_host_eri_erf(*shells, float(cutoff), omega, int(nthreads), ptr(out)))
     return out
 
 
@@ -647,10 +662,16 @@ def max_ang(basis: Basis) -> int:
     return max(int(s.ang) for s in basis.shells)
 
 
-def two_electron_device(basis: Basis, backend, cutoff: float = 1e-16):
+def two_electron_device(basis: Basis, backend, cutoff: float = 1e-16, omega: float | None = None):
     """(pq|rs) as a DEVICE tensor (nao,)*4 from libnbx's device engine (``nbx_eri_device``, csrc/eri.hip): the scheme,
-    pair data and screening of ``two_electron_native`` without the host tensor and its upload.  Shells of l <= 2."""
-    return backend.eri(basis, cutoff=cutoff)
+    pair data and screening of ``two_electron_native`` without the host tensor and its upload.  Shells of l <= 2.
+    ``omega``: the tensor over erf(omega r12) / r12 instead (``nbx_eri_device_erf``)."""
+    return backend.eri(basis, cutoff=cutoff, omega=_check_omega(omega))
+
+
+# the names the C entry points carry (nbx_host_eri / nbx_eri_device)
+eri_native = two_electron_native
+eri_device = two_electron_device
 
 
 def cholesky_device(basis: Basis, backend, tol: float = 1e-8, max_rank: int | None = None, cutoff: float = 1e-16):

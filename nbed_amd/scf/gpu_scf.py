@@ -685,6 +685,29 @@ class TaggedVeff(np.ndarray):
     ecoul = exc = vj = vk = None
 
 
+def _check_eri_lr(mf, eri_lr):
+    """The attenuated tensor of a range-separated Kohn-Sham object on its device (None when beta = 0)."""
+    if mf.beta == 0.0:
+        return None
+    if eri_lr is None:
+        raise ValueError(f"beta = {mf.beta}: a range-separated hybrid needs eri_lr, the tensor over erf(omega r12) / r12")
+    if mf._eri_factor_d is not None:
+        raise ValueError("a range-separated hybrid runs on dense tensors: eri_factor has no attenuated counterpart")
+    nao = mf._s_h.shape[0]
+    eri_lr = mf.be.asarray(eri_lr)
+    if tuple(eri_lr.shape) != (mf.shards.size, nao, nao, nao):
+        raise ValueError(f"eri_lr has shape {tuple(eri_lr.shape)}, expected {(mf.shards.size, nao, nao, nao)}")
+    return eri_lr
+
+
+def _k_lr_device(mf, dm_d):
+    """K_lr[x] (ndm, N, N) on device: the J/K build of ``jk_device`` on the attenuated tensor, J dropped."""
+    be, sh = mf.be, mf.shards
+    if hasattr(be, "jk_sym"):
+        return sh.all_reduce(be, be.jk_sym(mf._eri_lr_d, dm_d, sh.lo, sh.hi))[1:]
+    return sh.all_gather(be, be.jk(mf._eri_lr_d, dm_d, sh.lo, sh.hi), axis=1)[1:]
+
+
 class GpuUKS(GpuUHF, UKS):
     """Unrestricted Kohn-Sham object over dense S, hcore, (pq|rs): what the reference builds as
     ``dft.UKS`` (nbed/driver.py:163,303) and hands to ``huzinaga_scf`` (KS branch,
@@ -694,18 +717,31 @@ class GpuUKS(GpuUHF, UKS):
         veff[x] = J - hyb K[x] + v_xc[x],   ecoul = 1/2 tr(D_tot J),
         exc     = E_xc[D] - hyb/2 sum_x tr(D[x] K[x]),
 
-    and the semi-local part (E_xc, v_xc) comes from ``xc_provider(dm (2,N,N)) -> (E_xc, v_xc (2,N,N))``
+    or, for a range-separated hybrid (``beta`` != 0: ``eri_lr`` is the dense device tensor over erf(omega r12) / r12,
+    ``backend.eri(basis, omega=omega)``, and ``alpha`` another name for ``hyb``),
+
+        veff[x] = J - alpha K[x] - beta K_lr[x] + v_xc[x],
+        exc     = E_xc[D] - 1/2 sum_x tr(D[x] (alpha K[x] + beta K_lr[x])),
+
+    with K_lr from the same J/K kernels run on ``eri_lr`` (the J they return beside it is dropped: there is no K-only
+    kernel).  With beta = 0 nothing of this runs: the arithmetic and the launches are those above.  The semi-local part (E_xc, v_xc) comes from ``xc_provider(dm (2,N,N)) -> (E_xc, v_xc (2,N,N))``
     (``nbed_amd.xc``; None = no semi-local part, i.e. a pure exact-exchange hybrid: with hyb = 1
     this object is Hartree-Fock with Kohn-Sham bookkeeping)."""
 
     _device_kernel_ok = False
 
     def __init__(self, mol, ovlp, hcore, eri=None, backend=None, shards=None, xc="hf", hyb=1.0, xc_provider=None,
-                 eri_packed=None, eri_factor=None):
+                 eri_packed=None, eri_factor=None, omega=0.0, alpha=None, beta=0.0, eri_lr=None):
         super().__init__(mol, ovlp, hcore, eri, backend=backend, shards=shards, eri_packed=eri_packed, eri_factor=eri_factor)
         self.xc = xc
-        self.hyb = float(hyb)
+        self.hyb = float(hyb if alpha is None else alpha)
         self.xc_provider = xc_provider
+        self.omega, self.beta = float(omega), float(beta)
+        self._eri_lr_d = _check_eri_lr(self, eri_lr)
+
+    @property
+    def alpha(self) -> float:
+        return self.hyb
 
     def _veff_parts_device(self, dm_d):
         """(veff (2,N,N) device, ecoul, exc, jk (3,N,N) device) of a two-spin density."""
@@ -717,6 +753,11 @@ class GpuUKS(GpuUHF, UKS):
         tr_j = be.trace_prod(jk[0], dm_d[0]) + be.trace_prod(jk[0], dm_d[1])
         ecoul = 0.5 * float(tr_j)
         exc = -0.5 * self.hyb * float(be.trace_prod(jk[1:], dm_d).sum())
+        if self.beta != 0.0:  # veff[x] -= beta K_lr[x]
+            k_lr = _k_lr_device(self, dm_d)
+            for x in range(2):
+                be.axpby(-self.beta, k_lr[x], 1.0, veff[x])
+            exc -= 0.5 * self.beta * float(be.trace_prod(k_lr, dm_d).sum())
         if self.xc_provider is not None:
             e_sl, v_sl = self.xc_provider(be.to_host(dm_d))
             exc += float(e_sl)
@@ -774,9 +815,14 @@ class GpuRKS(_GpuSCF, RKS):
     fraction are libnbx builds; the semi-local part comes from ``xc_provider`` (``nbed_amd.xc``), called
     with the two equal spin halves of the density."""
 
-    def __init__(self, mol, ovlp, hcore, eri=None, backend=None, xc="lda,vwn", hyb=0.0, xc_provider=None):
+    def __init__(self, mol, ovlp, hcore, eri=None, backend=None, xc="lda,vwn", hyb=0.0, xc_provider=None, omega=0.0,
+                 alpha=None, beta=0.0, eri_lr=None):
+        """``omega``, ``alpha`` (another name for ``hyb``), ``beta``, ``eri_lr``: the exact part alpha K + beta K_lr of a
+        range-separated hybrid, as in ``GpuUKS``."""
         super().__init__(mol, ovlp, hcore, eri, backend=backend)
-        self.xc, self.hyb, self.xc_provider = xc, float(hyb), xc_provider
+        self.xc, self.hyb, self.xc_provider = xc, float(hyb if alpha is None else alpha), xc_provider
+        self.omega, self.beta = float(omega), float(beta)
+        self._eri_lr_d = _check_eri_lr(self, eri_lr)
 
     def get_veff(self, mol=None, dm=None, dm_last=0, vhf_last=0, hermi=1):
         be = self.be
@@ -785,6 +831,10 @@ class GpuRKS(_GpuSCF, RKS):
         veff = jk[0] - 0.5 * self.hyb * jk[1]
         ecoul = 0.5 * float(np.einsum("ij,ji->", jk[0], dm))
         exc = -0.25 * self.hyb * float(np.einsum("ij,ji->", jk[1], dm))
+        if self.beta != 0.0:
+            k_lr = be.to_host(_k_lr_device(self, be.asarray(dm[None])))[0]
+            veff = veff - 0.5 * self.beta * k_lr
+            exc -= 0.25 * self.beta * float(np.einsum("ij,ji->", k_lr, dm))
         if self.xc_provider is not None:
             e_sl, v_sl = self.xc_provider(np.array((0.5 * dm, 0.5 * dm)))
             exc += float(e_sl)

@@ -22,6 +22,14 @@ Functionals (libxc definitions, spin-polarised):
   * ``blyp``   Slater + B88 + LYP
   * ``b3lyp5`` 0.08 Slater + 0.72 B88 + 0.19 VWN5 + 0.81 LYP + 0.20 HF (libxc HYB_GGA_XC_B3LYP5: B3LYP with the
                Ceperley-Alder fit in place of VWN(RPA))
+  * ``cam-b3lyp`` (also ``camb3lyp``) 0.35 (Slater + B88) + 0.46 B88^sr(omega) + 0.19 VWN5 + 0.81 LYP, with the exact part
+               0.19 K + 0.46 K_lr(omega), omega = 0.33 (Yanai, Tew and Handy, Chem. Phys. Lett. 393, 51 (2004): alpha = 0.19,
+               beta = 0.46; K_lr is the exchange over erf(omega r12) / r12)
+  * ``lc-blyp``   B88^sr(omega) + LYP with the exact part K_lr(omega), omega = 0.33 (alpha = 0, beta = 1)
+               B88^sr is the B88 exchange (Slater part and gradient correction together) attenuated channel by channel in
+               the scheme of Iikura, Tsuneda, Yanai and Hirao (J. Chem. Phys. 115, 3540 (2001)).  The parameters of these
+               two are the papers': libxc is not installed here, so its HYB_GGA_XC_CAM_B3LYP / HYB_GGA_XC_LC_BLYP could not
+               be compared (DESIGN.md section 17 lists the converged energies for someone who can).
   * ``hf``     no semi-local part, 100 % exact exchange
 Energy densities are written once, in torch float64; their derivatives with respect to
 (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb) come from autograd, not from hand-derived formulas.
@@ -56,11 +64,28 @@ HYBRID_FRACTION = {"hf": 1.0, "b3lyp": 0.2, "lda": 0.0, "lda,vwn_rpa": 0.0, "lda
                    "b3lyp5": 0.2}
 
 
+#: range-separated hybrids: (omega, alpha, beta) of the exact part alpha K + beta K_lr(omega)
+RSH_PARAMETERS = {"cam-b3lyp": (0.33, 0.19, 0.46), "camb3lyp": (0.33, 0.19, 0.46), "lc-blyp": (0.33, 0.0, 1.0)}
+
+
 def hybrid_fraction(xc: str) -> float:
+    """The fraction of full-range exact exchange (alpha of ``rsh_parameters``; a range-separated hybrid adds
+    beta K_lr(omega) to it)."""
     key = str(xc).lower().replace(" ", "")
+    if key in RSH_PARAMETERS:
+        return RSH_PARAMETERS[key][1]
     if key not in HYBRID_FRACTION:
-        raise ValueError(f"functional {xc!r} is not in nbed_amd.xc ({sorted(HYBRID_FRACTION)})")
+        raise ValueError(f"functional {xc!r} is not in nbed_amd.xc ({sorted(HYBRID_FRACTION) + sorted(RSH_PARAMETERS)})")
     return HYBRID_FRACTION[key]
+
+
+def rsh_parameters(xc: str) -> tuple[float, float, float]:
+    """(omega, alpha, beta): the exact part of the functional is alpha K + beta K_lr(omega), K_lr over
+    erf(omega r12) / r12.  (0, hybrid fraction, 0) for every functional that is not range-separated."""
+    key = str(xc).lower().replace(" ", "")
+    if key in RSH_PARAMETERS:
+        return RSH_PARAMETERS[key]
+    return (0.0, hybrid_fraction(xc), 0.0)
 
 
 # ---------------------------------------------------------------------------------------------- grid
@@ -348,6 +373,80 @@ def _b88_correction(t, ra, rb, saa, sbb):
     return out
 
 
+def _ityh_coefficients(n: int = 16):
+    """c_1 .. c_n of F(a) = sum_m c_m t^m, t = 1 / (4 a^2): with that t every term of the closed form is a power series,
+    a sqrt(pi) erf(1 / (2a)) = sum_m (-t)^m / (m! (2m + 1)), b = sum_{m >= 1} (-t)^m / m!, a^2 = 1 / (4t), and collecting
+    powers gives c_m = -(8/3) (-1)^m [1 / (m! (2m + 1)) - 1 / (2 (m + 1)!) - 1 / (4 (m + 2)!)] (the orders t^-1 and t^0
+    cancel).  Exact fractions, rounded once."""
+    from fractions import Fraction
+
+    out = []
+    for m in range(1, n + 1):
+        f = math.factorial
+        out.append(float(Fraction(-8, 3) * (-1) ** m * (Fraction(1, f(m) * (2 * m + 1)) - Fraction(1, 2 * f(m + 1))
+                                                       - Fraction(1, 4 * f(m + 2)))))
+    return tuple(out)
+
+
+ITYH_SWITCH = 0.5  # a from which F(a) is summed as a series (see _ityh)
+ITYH_TINY = 1e-60  # a below which F = 1 - (8/3) sqrt(pi) a (omega = 0): 1 / a^4 overflows in autograd's closed form
+ITYH_SERIES = _ityh_coefficients()
+
+
+def _ityh(t, a):
+    """The attenuation factor of Iikura, Tsuneda, Yanai and Hirao,
+    F(a) = 1 - (8/3) a [sqrt(pi) erf(1 / (2a)) + 2a (b - c)], b = exp(-1 / (4 a^2)) - 1, c = 2 a^2 b + 1/2.
+    The bracket tends to 3/8 while F falls like 1 / (36 a^2), so in float64 the closed form loses 36 a^4 ulp: from
+    a = ITYH_SWITCH on F is summed as sixteen terms of its series in t = 1 / (4 a^2) <= 1.  Measured against 80 digits, F
+    and a F': closed form 1.3e-15 / 7e-16 relative at a = 0.5 (1.2e-14 at 0.7, 1e-7 at 100), series 1.2e-16 / 2.5e-16 at
+    0.5 and below 3e-16 above, but 6e-15 / 1.3e-13 at 0.4: the switch sits where both are at their best.  Below
+    a = ITYH_TINY F = 1 - (8/3) sqrt(pi) a.  Each branch is evaluated at a harmless argument where it is not taken, so
+    that autograd never meets an infinity."""
+    big, tiny = a >= ITYH_SWITCH, a < ITYH_TINY
+    tt = 0.25 / t.where(big, a, t.ones_like(a)) ** 2
+    series = t.zeros_like(a)
+    for c in reversed(ITYH_SERIES):
+        series = (series + c) * tt
+    ac = t.where(big | tiny, t.full_like(a, 0.25), a)
+    b = t.expm1(-0.25 / (ac * ac))
+    c = 2.0 * ac * ac * b + 0.5
+    closed = 1.0 - (8.0 / 3.0) * ac * (math.sqrt(math.pi) * t.erf(0.5 / ac) + 2.0 * ac * (b - c))
+    return t.where(big, series, t.where(tiny, 1.0 - (8.0 / 3.0) * math.sqrt(math.pi) * a, closed))
+
+
+def _b88_sr(t, ra, rb, saa, sbb, omega: float):
+    """Short-range B88 exchange: per spin channel the whole B88 exchange e = -rho^(4/3) G, G = cx + beta g(x), written as
+    -1/2 rho^(4/3) K, times F(a), a = omega / (2 k), k = sqrt(9 pi / K) rho^(1/3) (= (6 pi^2 rho)^(1/3) when K is the
+    Slater value).
+
+    Where F is summed as a series the energy is written through a alone: a = q sqrt(G) / rho^(1/3) with
+    q = omega sqrt(2) / (6 sqrt(pi)), so rho^(4/3) G = rho^2 a^2 / q^2 and e = -(rho^2 / q^2) Phi(a),
+    Phi = a^2 F = (1/4) sum_m c_m t^(m - 1).  In the form G F(a) autograd's derivative with respect to sigma is the sum
+    G' F + G F' da/dsigma = G' (F + a F' / 2), whose leading orders in t cancel (27 a^2 ulp lost: 3e-9 at a = 1e3); the
+    derivative of Phi has no such pair -- its constant term drops out exactly."""
+    if omega == 0.0:  # F(0) = 1
+        return _slater(t, ra, rb) + _b88_correction(t, ra, rb, saa, sbb)
+    cx = 1.5 * (3.0 / (4.0 * math.pi)) ** (1.0 / 3.0)
+    beta = 0.0042
+    q = omega * math.sqrt(2.0) / (6.0 * math.sqrt(math.pi))
+    out = 0.0
+    for r, s in ((ra, saa), (rb, sbb)):
+        r13 = r ** (1.0 / 3.0)
+        r43 = r13 * r
+        x = t.sqrt(s) / r43
+        big_g = cx + beta * x * x / (1.0 + 6.0 * beta * x * t.asinh(x))
+        a = q * t.sqrt(big_g) / r13
+        big = a >= ITYH_SWITCH
+        tt = 0.25 / t.where(big, a, t.ones_like(a)) ** 2
+        phi = t.zeros_like(a)
+        for c in reversed(ITYH_SERIES[1:]):
+            phi = (phi + c) * tt
+        phi = 0.25 * (phi + ITYH_SERIES[0])
+        small = r43 * big_g * _ityh(t, t.where(big, t.full_like(a, 0.25), a))
+        out = out - t.where(big, r * r / (q * q) * phi, small)
+    return out
+
+
 def _vwn_rpa(t, ra, rb):
     """Vosko-Wilk-Nusair correlation, the fit to the RPA data (libxc LDA_C_VWN_RPA; Gaussian's "VWN3")."""
     rho = ra + rb
@@ -484,12 +583,22 @@ def _pbe_c(t, ra, rb, saa, sab, sbb):
     return rho * (eps + g3 * t.log1p(em * frac))
 
 
-def energy_density(xc: str, ra, rb, saa, sab, sbb):
-    """Semi-local exchange-correlation energy per volume (torch tensors); None for ``hf``."""
+def energy_density(xc: str, ra, rb, saa, sab, sbb, omega: float | None = None):
+    """Semi-local exchange-correlation energy per volume (torch tensors); None for ``hf``.  ``omega``: another range
+    separation than the functional's own (range-separated hybrids only)."""
     t = _torch()
     key = str(xc).lower().replace(" ", "")
     if key == "hf":
         return None
+    if key in RSH_PARAMETERS:
+        w, alpha, beta = RSH_PARAMETERS[key]
+        w = w if omega is None else float(omega)
+        if key == "lc-blyp":
+            return _b88_sr(t, ra, rb, saa, sbb, w) + _lyp(t, ra, rb, saa, sab, sbb)
+        return ((1.0 - alpha - beta) * (_slater(t, ra, rb) + _b88_correction(t, ra, rb, saa, sbb))
+                + beta * _b88_sr(t, ra, rb, saa, sbb, w) + 0.19 * _vwn5(t, ra, rb) + 0.81 * _lyp(t, ra, rb, saa, sab, sbb))
+    if omega is not None:
+        raise ValueError(f"functional {xc!r} is not range-separated: it takes no omega")
     if key in ("lda", "lda,vwn_rpa"):
         return _slater(t, ra, rb) + _vwn_rpa(t, ra, rb)
     if key in ("lda,vwn", "lda,vwn5", "svwn"):
@@ -529,6 +638,7 @@ class XCProvider:
         t = _torch()
         self.xc = str(xc).lower().replace(" ", "")
         self.hyb = hybrid_fraction(self.xc)
+        self.omega, self.alpha, self.beta = rsh_parameters(self.xc)
         if device is None:
             device = "cuda" if t.cuda.is_available() else "cpu"
         self.device = t.device(device)
@@ -571,11 +681,14 @@ class XCProvider:
         nbx_xc_functional (analytic energy density and derivatives, weights folded in, E_xc reduced on the device),
         nbx_xc_vmat (the potential matrix with its ``half`` factor built on the fly).  Three kernels and two small
         reductions per evaluation; the host sees E_xc, the electron count and the (2, nao, nao) result."""
-        from ._nbx import XC_CODES
+        from ._nbx import XC_CODES, XC_RS_CODES
 
         dmd = be.asarray(0.5 * (dm + dm.transpose(0, 2, 1)))
         rho, grad = be.xc_rho(self._ao, self._dao, dmd)
-        vr, vec, sums = be.xc_functional(XC_CODES[self.xc], rho, grad, self._w, self.RHO_FLOOR)
+        if self.xc in XC_RS_CODES:
+            vr, vec, sums = be.xc_functional_rs(XC_RS_CODES[self.xc], self.omega, rho, grad, self._w, self.RHO_FLOOR)
+        else:
+            vr, vec, sums = be.xc_functional(XC_CODES[self.xc], rho, grad, self._w, self.RHO_FLOOR)
         vxc = be.xc_vmat(self._ao, self._dao, vr, vec)
         sums_h = be.to_host(sums)
         self.nelec_last = float(sums_h[1])
