@@ -738,6 +738,36 @@ int nbx_mu_cycle_fock_post(nbx_ctx* ctx, const nbx_huz_state* st, const double* 
 int nbx_xc_functional_rs(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho, const double* d_grad,
                          const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
                          size_t work_bytes);
+/* Meta-GGAs: the same three passes with the kinetic-energy density tau_x = 1/2 sum_i |grad psi_i|^2 carried through
+ * them (what libxc evaluates behind dft.UKS.get_veff, nbed/driver.py:155-191, 315-431, 845-852, 1138-1231, when
+ * xc_functional names a meta-GGA).  Entry points of their own: the ones above keep their arguments and their codes.
+ * nbx_xc_rho_tau:  nbx_xc_rho plus d_tau (2, npts), tau_x = 1/2 sum_a diag(dao_a D_x dao_a^T).  For every 16-column tile
+ *   the slab of D is staged in LDS once and multiplied by the fragments of ao and of each dao_a in turn, each product
+ *   reduced in the epilogue against its own operand; d_rho and d_grad come out bit for bit as nbx_xc_rho's.  nao <= 640
+ *   (NBX_E_UNSUPPORTED beyond).
+ * nbx_xc_functional_mgga:  nbx_xc_functional's arguments plus d_tau (2, npts) in and d_vt (2, npts) = w dE/dtau_x out.
+ *   NBX_XC_TPSS = TPSS exchange + TPSS correlation (Tao, Perdew, Staroverov and Scuseria, Phys. Rev. Lett. 91, 146401
+ *   (2003)); NBX_XC_TPSSH = 0.9 TPSS exchange + TPSS correlation (Staroverov, Scuseria, Tao and Perdew, J. Chem. Phys.
+ *   119, 12129 (2003)) without its 0.1 exact exchange.  Every other code: NBX_E_INVALID (and nbx_xc_functional /
+ *   nbx_xc_functional_rs refuse these two).  Conventions besides nbx_xc_functional's: wherever z = tau_W / tau is formed,
+ *   tau is clamped from below at tau_W = sigma / (8 n) of the same clamped quantities -- each spin channel's own in the
+ *   exchange, the totals in the correlation -- by the float64 test tau >= sigma / (8 n) * (1 - 1e-10); where it fails
+ *   z = 1 and alpha = 0 are constants (the margin: a one-orbital density sits on the clamp at every point, and the
+ *   potential has a kink there).  "The larger of" eps_PBE(n_s, 0, grad n_s, 0) and eps_PBE is the first where it is >= the
+ *   second.  DESIGN.md section 18.
+ * nbx_xc_vmat_tau:  nbx_xc_vmat with the products sum_a dao_a^T (d_vt[x] / 4 dao_a) added to V_x before V + V^T (after
+ *   it: 1/2 int v_tau grad phi_m . grad phi_n); with d_vt = 0 the result is nbx_xc_vmat's bit for bit.  d_work:
+ *   nbx_xc_vmat_tau_worksize() bytes. */
+#define NBX_XC_TPSS 32
+#define NBX_XC_TPSSH 33
+int nbx_xc_rho_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao, const double* d_dm,
+                   double* d_rho, double* d_grad, double* d_tau);
+int nbx_xc_functional_mgga(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
+                           const double* d_tau, const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_vt,
+                           double* d_sums, void* d_work, size_t work_bytes);
+size_t nbx_xc_vmat_tau_worksize(int64_t npts, int64_t nao);
+int nbx_xc_vmat_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao, const double* d_vr,
+                    const double* d_vec, const double* d_vt, double* d_vxc, void* d_work, size_t work_bytes);
 int nbx_xc_rho(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao, const double* d_dm,
                double* d_rho, double* d_grad);
 size_t nbx_xc_functional_worksize(int64_t npts);

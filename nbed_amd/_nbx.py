@@ -28,6 +28,7 @@ HUZ_JK_PACKED, HUZ_JK_SYM = 0, 1
 XC_CODES = {"slater": 0, "lda": 1, "lda,vwn_rpa": 1, "lda,vwn": 2, "lda,vwn5": 2, "svwn": 2, "b3lyp": 3, "lda,pw_mod": 4,
             "pbe": 5, "pbe,pbe": 5, "pbeh": 6, "pbe1pbe": 6, "blyp": 7, "b3lyp5": 8}
 XC_RS_CODES = {"cam-b3lyp": 16, "camb3lyp": 16, "lc-blyp": 17}  # nbx_xc_functional_rs (NBX_XC_CAM_B3LYP, NBX_XC_LC_BLYP)
+XC_MGGA_CODES = {"tpss": 32, "tpssh": 33}  # nbx_xc_functional_mgga (NBX_XC_TPSS, NBX_XC_TPSSH)
 
 PROF_JK_DENSE, PROF_AO2MO_Q1, PROF_AO2MO, PROF_EIGH, PROF_SVD, PROF_GEMM = range(6)
 PROF_ERI = 7  # the class launches of nbx_eri_device (nbx_eri_class_ms)
@@ -189,6 +190,10 @@ SIGNATURES = {
     "nbx_xc_functional": (c_int, [_P, c_int, c_int64, _P, _P, _P, c_double, _P, _P, _P, _P, c_size_t]),
     "nbx_xc_functional_rs": (c_int, [_P, c_int, c_double, c_int64, _P, _P, _P, c_double, _P, _P, _P, _P, c_size_t]),
     "nbx_xc_vmat_worksize": (c_size_t, [c_int64, c_int64]),
+    "nbx_xc_rho_tau": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P]),
+    "nbx_xc_functional_mgga": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P, c_double, _P, _P, _P, _P, _P, c_size_t]),
+    "nbx_xc_vmat_tau_worksize": (c_size_t, [c_int64, c_int64]),
+    "nbx_xc_vmat_tau": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t]),
     "nbx_xc_vmat": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_size_t]),
     "nbx_purify_worksize": (c_size_t, [c_int64, c_int64]),
     "nbx_purify": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, _P, c_size_t, c_int, _P]),

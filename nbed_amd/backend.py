@@ -1216,6 +1216,37 @@ class HipBackend:
                    work.numel())
         return out
 
+    def xc_rho_tau(self, ao, dao, dm):
+        """``xc_rho`` plus the kinetic-energy densities tau (2, G) = 1/2 sum_a diag(dao_a D dao_a^T) (nbx_xc_rho_tau: the
+        slab of D staged once per column tile and multiplied by the fragments of ao and of each dao_a; ``rho`` and
+        ``grad`` are ``xc_rho``'s bit for bit)."""
+        g, nao = int(ao.shape[0]), int(ao.shape[1])
+        rho, grad, tau = self.empty((2, g)), self.empty((2, 3, g)), self.empty((2, g))
+        self._call("nbx_xc_rho_tau", g, nao, self._p(ao), self._p(dao), self._p(dm), self._p(rho), self._p(grad), self._p(tau))
+        return rho, grad, tau
+
+    def xc_functional_mgga(self, code: int, rho, grad, tau, w, rho_floor: float):
+        """``xc_functional`` for a meta-GGA (nbx_xc_functional_mgga: ``code`` from ``_nbx.XC_MGGA_CODES``):
+        ``(vr (2, G), vec (2, 3, G), vt (2, G) = w dE/dtau, sums)``."""
+        g = int(rho.shape[-1])
+        vr, vec, vt, sums = self.empty((2, g)), self.empty((2, 3, g)), self.empty((2, g)), self.empty(2)
+        nbytes = int(self.lib.nbx_xc_functional_worksize(g))
+        work = self._workspace("xc_fn", nbytes)
+        self._call("nbx_xc_functional_mgga", int(code), g, self._p(rho), self._p(grad), self._p(tau), self._p(w),
+                   float(rho_floor), self._p(vr), self._p(vec), self._p(vt), self._p(sums), self._p(work), work.numel())
+        return vr, vec, vt, sums
+
+    def xc_vmat_tau(self, ao, dao, vr, vec, vt):
+        """``xc_vmat`` with sum_a dao_a^T (vt / 4 dao_a) added before the symmetrisation (nbx_xc_vmat_tau: after it,
+        1/2 int v_tau grad phi_m . grad phi_n)."""
+        g, nao = int(ao.shape[0]), int(ao.shape[1])
+        out = self.empty((2, nao, nao))
+        nbytes = int(self.lib.nbx_xc_vmat_tau_worksize(g, nao))
+        work = self._workspace("xc_vmat", nbytes)
+        self._call("nbx_xc_vmat_tau", g, nao, self._p(ao), self._p(dao), self._p(vr), self._p(vec), self._p(vt), self._p(out),
+                   self._p(work), work.numel())
+        return out
+
     def ao_table(self, basis):
         """The shells of an ``integrals.Basis`` flattened into the device arrays nbx_eval_ao reads."""
         torch = self.torch

@@ -772,3 +772,528 @@ extern "C" int nbx_xc_vmat(nbx_ctx* ctx, int64_t npts, int64_t nao, const double
     NBX_LAUNCH_CHECK();
     return NBX_OK;
 }
+
+// =============================================================================================== meta-GGAs
+// The same three passes with the kinetic-energy density tau_x = 1/2 sum_i |grad psi_i|^2 carried through them
+// (nbx_xc_rho_tau, nbx_xc_functional_mgga, nbx_xc_vmat_tau); the kernels above are untouched.
+namespace {
+
+// ------------------------------------------------------------------------------------------------ density pass with tau
+// xc_rho_kernel with three more products per column tile: after c = ao D (same fragments, same order, same epilogue:
+// rho and grad rho come out bit for bit) the slab of D that is already in LDS is multiplied by the fragments of dao_x,
+// dao_y and dao_z in turn (streamed: 3 x 40 doubles would not fit beside the ao fragments), and each product is reduced
+// against the dao_a values the epilogue of rho has just read: tau = 1/2 sum_a sum_m (dao_a D)[g][m] dao_a[g][m].
+// The passes are sequential inside the tile loop: two accumulators live at a time.           -- MFMA bound, 4 x xc_rho
+template <int AREG>
+__global__ __launch_bounds__(256) void xc_rho_tau_kernel(int64_t npts, int nao, const double* __restrict__ ao,
+                                                         const double* __restrict__ dao, const double* __restrict__ dm,
+                                                         double* __restrict__ rho, double* __restrict__ grad,
+                                                         double* __restrict__ tau) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int KP = (nao + 3) & ~3, NT = (nao + 15) >> 4, NK = KP >> 2;
+    double* ds0 = smem;             // [KP][16]  D_alpha[:, tile]
+    double* ds1 = smem + KP * 16;   // [KP][16]  D_beta
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fk = lane >> 4;
+    const int64_t gw = (int64_t)blockIdx.x * 64 + wave * 16;
+    const int64_t plane = npts * (int64_t)nao, n2 = (int64_t)nao * nao;
+    const int64_t ga = gw + fr;  // the A-fragment row of this lane
+    const bool a_ok = ga < npts;
+    const double* arow = ao + (a_ok ? ga : 0) * nao;
+    double afr[AREG > 0 ? AREG : 1];
+    if (AREG > 0) {
+#pragma unroll
+        for (int j = 0; j < AREG; ++j) {
+            const int k = 4 * j + fk;
+            afr[j] = (a_ok && k < nao) ? arow[k] : 0.0;
+        }
+    }
+    double pr[2][4], px[2][4], py[2][4], pz[2][4], pt[2][4];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pr[x][r] = px[x][r] = py[x][r] = pz[x][r] = pt[x][r] = 0.0;
+
+    for (int ct = 0; ct < NT; ++ct) {
+        __syncthreads();  // the previous tile's fragments have been read
+        for (int e = threadIdx.x; e < KP * 16; e += 256) {
+            const int k = e >> 4, c = 16 * ct + (e & 15);
+            const bool in = k < nao && c < nao;
+            ds0[e] = in ? dm[(int64_t)k * nao + c] : 0.0;
+            ds1[e] = in ? dm[n2 + (int64_t)k * nao + c] : 0.0;
+        }
+        __syncthreads();
+        xc_v4 acc0 = (xc_v4){0.0, 0.0, 0.0, 0.0}, acc1 = (xc_v4){0.0, 0.0, 0.0, 0.0};
+        if (AREG > 0) {
+#pragma unroll
+            for (int j = 0; j < AREG; ++j) {
+                if (j < NK) {
+                    const int k = 4 * j + fk;
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[j], ds0[k * 16 + fr], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[j], ds1[k * 16 + fr], acc1, 0, 0, 0);
+                }
+            }
+        } else {
+            for (int j = 0; j < NK; ++j) {
+                const int k = 4 * j + fk;
+                const double a = (a_ok && k < nao) ? arow[k] : 0.0;
+                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, ds0[k * 16 + fr], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, ds1[k * 16 + fr], acc1, 0, 0, 0);
+            }
+        }
+        // epilogue: this tile of c against the same tile of ao / dao; the dao values stay for the tau products
+        const int m = 16 * ct + fr;
+        double dv[3][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dv[0][r] = dv[1][r] = dv[2][r] = 0.0;
+        if (m < nao) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t g = gw + fk + 4 * r;
+                if (g < npts) {
+                    const int64_t off = g * nao + m;
+                    const double v0 = ao[off], vx = dao[off], vy = dao[plane + off], vz = dao[2 * plane + off];
+                    pr[0][r] = fma(acc0[r], v0, pr[0][r]);
+                    px[0][r] = fma(acc0[r], vx, px[0][r]);
+                    py[0][r] = fma(acc0[r], vy, py[0][r]);
+                    pz[0][r] = fma(acc0[r], vz, pz[0][r]);
+                    pr[1][r] = fma(acc1[r], v0, pr[1][r]);
+                    px[1][r] = fma(acc1[r], vx, px[1][r]);
+                    py[1][r] = fma(acc1[r], vy, py[1][r]);
+                    pz[1][r] = fma(acc1[r], vz, pz[1][r]);
+                    dv[0][r] = vx, dv[1][r] = vy, dv[2][r] = vz;
+                }
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double* drow = dao + a * plane + (a_ok ? ga : 0) * nao;
+            xc_v4 t0 = (xc_v4){0.0, 0.0, 0.0, 0.0}, t1 = (xc_v4){0.0, 0.0, 0.0, 0.0};
+            for (int j = 0; j < NK; ++j) {
+                const int k = 4 * j + fk;
+                const double d = (a_ok && k < nao) ? drow[k] : 0.0;
+                t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(d, ds0[k * 16 + fr], t0, 0, 0, 0);
+                t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(d, ds1[k * 16 + fr], t1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {  // (dv = 0 outside the arrays)
+                pt[0][r] = fma(t0[r], dv[a][r], pt[0][r]);
+                pt[1][r] = fma(t1[r], dv[a][r], pt[1][r]);
+            }
+        }
+    }
+    // sum over the 16 lanes (columns) that share the rows fk + 4 r: xor shuffles stay inside the 16-lane group
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double a = pr[x][r], b = px[x][r], c = py[x][r], d = pz[x][r], t = pt[x][r];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                a += __shfl_xor(a, o, 64);
+                b += __shfl_xor(b, o, 64);
+                c += __shfl_xor(c, o, 64);
+                d += __shfl_xor(d, o, 64);
+                t += __shfl_xor(t, o, 64);
+            }
+            const int64_t g = gw + fk + 4 * r;
+            if (fr == 0 && g < npts) {
+                rho[x * npts + g] = a;
+                grad[(3 * x + 0) * npts + g] = 2.0 * b;
+                grad[(3 * x + 1) * npts + g] = 2.0 * c;
+                grad[(3 * x + 2) * npts + g] = 2.0 * d;
+                tau[x * npts + g] = 0.5 * t;
+            }
+        }
+}
+
+// ------------------------------------------------------------------------------------------------ TPSS
+// Conventions (nbed_amd.xc, "Meta-GGA conventions"): wherever z = tau_W / tau is formed, tau is clamped from below at
+// tau_W = sigma / (8 n) of the same clamped quantities by the test tau >= sigma / (8 n) * XC_TPSS_CLAMP; where it fails
+// z = 1 and alpha = 0 are constants.  XC_TPSS_CLAMP = 1 - 1e-10: a one-orbital density has tau = tau_W at every point up
+// to the rounding of the density pass, and the potential has a kink at the clamp -- the margin keeps such points on one
+// side of it (z <= 1 + 1e-10).  "The larger of" a and b is a where a >= b.
+//
+// TPSS exchange of one spin channel (spin-scaled: E_x[n_a, n_b] = 1/2 E_x[2 n_a] + 1/2 E_x[2 n_b], tau doubled too):
+//   e = -cx rho^(4/3) F(p, z),  F = 1 + kappa - kappa / (1 + x / kappa) = 1 + kappa x / (kappa + x),
+//   p = sigma / (4 (6 pi^2)^(2/3) rho^(8/3)),  z = sigma / (8 rho tau),
+//   alpha = (5p/3)(1/z - 1) = (tau - tau_W) / (cF rho^(5/3)),  cF = (3/10)(6 pi^2)^(2/3)   (no 0 x inf at a zero gradient)
+//   q_b = (9/20)(alpha - 1) / sqrt(1 + b alpha (alpha - 1)) + 2p/3
+//   x = N / (1 + sqrt(e) p)^2,  N = [10/81 + c z^2 / (1 + z^2)^2] p + (146/2025) q_b^2 - (73/405) q_b sqrt((9/50) z^2 + p^2/2)
+//       + (10/81)^2 p^2 / kappa + 2 sqrt(e) (10/81) (9/25) z^2 + e mu p^3
+// The chain rule runs through (p, z, alpha), each with its derivatives with respect to (rho, sigma, tau).
+constexpr double XC_TPSS_CLAMP = 1.0 - 1e-10;
+
+__device__ __forceinline__ void xc_tpss_x(double s, double r, double sg, double tau, double& e, double& vr, double& vs,
+                                          double& vt) {
+    const double cx = 0.9305257363491002;    // (3/2) (3 / (4 pi))^(1/3)
+    const double c2 = 0.016455307846020558;  // 1 / (4 (6 pi^2)^(2/3))
+    const double cf = 4.557799872345596;     // (3/10) (6 pi^2)^(2/3)
+    const double kappa = 0.804, b = 0.40, c = 1.59096, ee = 1.537, mu = 0.21951;
+    const double se = 1.239758040909596;     // sqrt(e)
+    const double k1 = 146.0 / 2025.0, k2 = 73.0 / 405.0, k3 = (10.0 / 81.0) * (10.0 / 81.0) / kappa;
+    const double k4 = 2.0 * se * (10.0 / 81.0) * 0.36, k5 = ee * mu;
+    const double r13 = cbrt(r), r43 = r13 * r, r53 = r13 * r13 * r, r83 = r43 * r43;
+    const double p = c2 * sg / r83;
+    const double tw = sg / (8.0 * r);
+    double z = 1.0, alpha = 0.0, z_r = 0.0, z_s = 0.0, z_t = 0.0, a_r = 0.0, a_s = 0.0, a_t = 0.0;
+    if (tau >= tw * XC_TPSS_CLAMP) {
+        z = tw / tau;
+        a_t = 1.0 / (cf * r53);
+        alpha = (tau - tw) * a_t;
+        z_r = -z / r, z_s = 1.0 / (8.0 * r * tau), z_t = -z / tau;
+        a_s = -a_t / (8.0 * r);
+        a_r = (tw / r) * a_t - (5.0 / 3.0) * alpha / r;
+    }
+    const double z2 = z * z, am1 = alpha - 1.0;
+    const double w = fma(b * alpha, am1, 1.0), sw = sqrt(w);
+    const double qb = 0.45 * am1 / sw + (2.0 / 3.0) * p;
+    // d/dalpha of (alpha - 1) / sqrt(w) is (1 - b / 2 + b alpha / 2) / w^(3/2): as 1 / sqrt(w) - (alpha - 1) w' / (2 w^(3/2))
+    // its two terms cancel to 1 / alpha of their size
+    const double qb_a = 0.45 * fma(0.5 * b, alpha, 1.0 - 0.5 * b) / (w * sw);
+    const double opz = 1.0 + z2;
+    const double t1 = 10.0 / 81.0 + c * z2 / (opz * opz);
+    const double t1_z = 2.0 * c * z * (1.0 - z2) / (opz * opz * opz);
+    const double sq = sqrt(fma(0.18, z2, 0.5 * p * p));
+    const double sq_z = 0.18 * z / sq, sq_p = 0.5 * p / sq;
+    const double lin = 2.0 * k1 * qb - k2 * sq;  // dN/dq_b
+    const double N = t1 * p + k1 * qb * qb - k2 * qb * sq + k3 * p * p + k4 * z2 + k5 * p * p * p;
+    const double N_p = t1 + (2.0 / 3.0) * lin - k2 * qb * sq_p + 2.0 * k3 * p + 3.0 * k5 * p * p;
+    const double N_z = t1_z * p - k2 * qb * sq_z + 2.0 * k4 * z;
+    const double N_a = lin * qb_a;
+    const double d1 = fma(se, p, 1.0), Dn = d1 * d1;
+    const double x = N / Dn;
+    const double x_p = N_p / Dn - 2.0 * se * x / d1, x_z = N_z / Dn, x_a = N_a / Dn;
+    const double kx = kappa + x;
+    const double F = 1.0 + kappa * x / kx, Fx = kappa * kappa / (kx * kx);
+    const double dF_r = Fx * (x_p * (-(8.0 / 3.0) * p / r) + x_z * z_r + x_a * a_r);
+    const double dF_s = Fx * (x_p * (c2 / r83) + x_z * z_s + x_a * a_s);
+    const double dF_t = Fx * (x_z * z_t + x_a * a_t);
+    e += s * (-cx * r43 * F);
+    vr += s * (-cx * ((4.0 / 3.0) * r13 * F + r43 * dF_r));
+    vs += s * (-cx * r43 * dF_s);
+    vt += s * (-cx * r43 * dF_t);
+}
+
+// eps_PBE(n_s, 0, grad n_s, 0) per electron with its derivatives with respect to (n_s, sigma_ss): xc_pbe_c at zeta = 1
+// written without the empty channel (f(zeta) = 1, zeta^4 = 1, 1 - zeta^4 = 0: eps_PW = eps_1; phi = 2^(-1/3)), so that
+// nothing is differentiated with respect to it.
+__device__ __forceinline__ void xc_pbe_c_pol(double r, double sg, double& eps, double& d_r, double& d_s) {
+    const double gamma = 0.031090690869654895, bg = 2.1461263399673646, ct = 0.0634682060977037;
+    const double phi2 = 0.6299605249474366;  // 2^(-2/3)
+    const double g3 = 0.5 * gamma;
+    const double x = sqrt(cbrt(0.238732414637843 / r));
+    const double rs = x * x;
+    double e1, de1;
+    xc_pw_g(x, 0.01554535, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517, e1, de1);
+    const double kt = ct / (phi2 * r * r * cbrt(r));
+    const double T = kt * sg;
+    const double em = expm1(-e1 / g3);
+    const double y = bg / em * T;
+    const double D = fma(y, y + 1.0, 1.0), D2 = D * D;
+    const double X = em * (y > 1.0 ? 1.0 - 1.0 / D : y * (1.0 + y) / D);
+    const double H = g3 * log1p(X);
+    const double hx = g3 / (1.0 + X);
+    const double XT = bg * fma(2.0, y, 1.0) / D2;
+    const double q = y * y * y * (2.0 + y) * (1.0 + em) / D2 / (1.0 + X);
+    eps = e1 + H;
+    d_s = hx * XT * kt;
+    d_r = (-(rs / 3.0) * de1 - (7.0 / 3.0) * hx * XT * T + q * rs * de1 / 3.0) / r;
+}
+
+// TPSS correlation: e = n eps (1 + d eps z^3) with eps = eps_revPKZB,
+//   eps_revPKZB = eps_PBE (1 + C z^2) - (1 + C) z^2 sum_s (n_s / n) max(eps_PBE(n_s, 0, grad n_s, 0), eps_PBE),
+//   z = sigma / (8 n tau) of the totals,  C = (0.53 + 0.87 zeta^2 + 0.50 zeta^4 + 2.26 zeta^6) / (1 + X)^4,
+//   X = xi^2 ((1 + zeta)^(-4/3) + (1 - zeta)^(-4/3)) / 2 = Q h / (2 (3 pi^2)^(2/3) n^(14/3)),
+//   Q = n_b^2 sigma_aa - 2 n_a n_b sigma_ab + n_a^2 sigma_bb (= n^4 |grad zeta|^2 / 4),  h = up^(-4/3) + dn^(-4/3),
+// 1 +- zeta = 2 n_s / n never by subtraction; C is the fourth power of 1 / (1 + X): where a fully polarised point has a
+// gradient of zeta, X is 1e18 and C underflows towards 0 with finite derivatives.  d[0..5]: the derivatives of e with
+// respect to (n_a, n_b, sigma_aa, sigma_ab, sigma_bb, tau); eps_PBE and its derivatives come from xc_pbe_c.
+__device__ __forceinline__ void xc_tpss_c(double ra, double rb, double saa, double sab, double sbb, double tau, double& e,
+                                          double (&d)[6]) {
+    const double dd = 2.8;
+    XcDer P = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    xc_pbe_c(1.0, ra, rb, saa, sab, sbb, P);
+    const double n = ra + rb, n2 = n * n;
+    const double E = P.e / n;
+    const double dE[6] = {(P.va - E) / n, (P.vb - E) / n, P.vaa / n, P.vab / n, P.vbb / n, 0.0};
+    double Ea, Ea_r, Ea_s, Eb, Eb_r, Eb_s;
+    xc_pbe_c_pol(ra, saa, Ea, Ea_r, Ea_s);
+    xc_pbe_c_pol(rb, sbb, Eb, Eb_r, Eb_s);
+    const bool sa = Ea >= E, sb = Eb >= E;
+    const double A = sa ? Ea : E, B = sb ? Eb : E;
+    const double fa = ra / n, fb = rb / n;
+    const double S = fa * A + fb * B;
+    // z of the totals
+    const double st = saa + 2.0 * sab + sbb;
+    const double tw = st / (8.0 * n);
+    double z = 1.0, dz[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (tau >= tw * XC_TPSS_CLAMP) {
+        const double zk = 1.0 / (8.0 * n * tau);
+        z = st * zk;
+        dz[0] = dz[1] = -z / n;
+        dz[2] = dz[4] = zk;
+        dz[3] = 2.0 * zk;
+        dz[5] = -z / tau;
+    }
+    const double z2 = z * z, z3 = z2 * z;
+    // C(zeta, xi)
+    const double zeta = (ra - rb) / n, up = 2.0 * ra / n, dn = 2.0 * rb / n, zz = zeta * zeta;
+    const double num = fma(zz, fma(zz, fma(zz, 2.26, 0.50), 0.87), 0.53);
+    const double dnum = zeta * fma(zz, fma(zz, 13.56, 2.0), 1.74);
+    const double dzeta[2] = {dn / n, -up / n};
+    const double Q = rb * rb * saa - 2.0 * ra * rb * sab + ra * ra * sbb;
+    const double hu = 1.0 / (cbrt(up) * up), hd = 1.0 / (cbrt(dn) * dn);
+    const double h = hu + hd;
+    const double h_up = -(4.0 / 3.0) * hu / up, h_dn = -(4.0 / 3.0) * hd / dn;
+    const double dh[2] = {(h_up - h_dn) * dn / n, (h_dn - h_up) * up / n};
+    const double cn = cbrt(n);
+    const double gq = 1.0 / (19.141560001254607 * n2 * n2 * cn * cn);  // 1 / (2 (3 pi^2)^(2/3) n^(14/3))
+    const double X = Q * h * gq;
+    const double dQ[2] = {2.0 * (ra * sbb - rb * sab), 2.0 * (rb * saa - ra * sab)};
+    const double dX[6] = {(dQ[0] * h + Q * dh[0]) * gq - (14.0 / 3.0) * X / n, (dQ[1] * h + Q * dh[1]) * gq - (14.0 / 3.0) * X / n,
+                          rb * rb * h * gq, -2.0 * ra * rb * h * gq, ra * ra * h * gq, 0.0};
+    const double inv = 1.0 / (1.0 + X), inv2 = inv * inv, i4 = inv2 * inv2;
+    const double C = num * i4;
+    const double rev = E * fma(C, z2, 1.0) - (1.0 + C) * z2 * S;
+    const double g1 = fma(2.0 * dd * rev, z3, 1.0);
+    const double eps = rev * fma(dd * rev, z3, 1.0);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const double dC = (i < 2 ? dnum * dzeta[i] * i4 : 0.0) - 4.0 * C * inv * dX[i];
+        double dA = sa ? 0.0 : dE[i], dB = sb ? 0.0 : dE[i];
+        if (sa && i == 0) dA = Ea_r;
+        if (sa && i == 2) dA = Ea_s;
+        if (sb && i == 1) dB = Eb_r;
+        if (sb && i == 4) dB = Eb_s;
+        double dS = fa * dA + fb * dB;
+        if (i == 0) dS += rb / n2 * (A - B);
+        if (i == 1) dS += ra / n2 * (B - A);
+        const double dz2 = 2.0 * z * dz[i];
+        const double drev = dE[i] * fma(C, z2, 1.0) + E * (dC * z2 + C * dz2) - (dC * z2 + (1.0 + C) * dz2) * S -
+                            (1.0 + C) * z2 * dS;
+        const double deps = drev * g1 + dd * rev * rev * 3.0 * z2 * dz[i];
+        d[i] = n * deps + (i < 2 ? eps : 0.0);
+    }
+    e = n * eps;
+}
+
+// nbx_xc_functional's kernel for the meta-GGAs: CODE = NBX_XC_TPSS / NBX_XC_TPSSH (0.9 of the exchange; the 0.1 of exact
+// exchange is the caller's).  Inputs, conventions and outputs of xc_functional_kernel, plus tau (2, npts) in and
+//   vt[x][g] = w keep dE/dtau_x
+// out.  The exchange clamps each channel's tau against its own tau_W, the correlation tau_a + tau_b against the total's.
+template <int CODE>
+__global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_mgga_kernel(int64_t npts, const double* __restrict__ rho,
+                                                                           const double* __restrict__ grad,
+                                                                           const double* __restrict__ tau,
+                                                                           const double* __restrict__ w, double rho_floor,
+                                                                           double* __restrict__ vr, double* __restrict__ vec,
+                                                                           double* __restrict__ vt, double* __restrict__ part) {
+    __shared__ double red[17];
+    const int64_t g = (int64_t)blockIdx.x * XC_FN_THREADS + threadIdx.x;
+    double e_w = 0.0, n_w = 0.0;
+    if (g < npts) {
+        const double r0 = rho[g], r1 = rho[npts + g], wg = w[g], ta = tau[g], tb = tau[npts + g];
+        const double gax = grad[g], gay = grad[npts + g], gaz = grad[2 * npts + g];
+        const double gbx = grad[3 * npts + g], gby = grad[4 * npts + g], gbz = grad[5 * npts + g];
+        n_w = wg * (r0 + r1);
+        const double keep = (r0 + r1) > rho_floor ? 1.0 : 0.0;
+        const double ra = fmax(r0, 0.5 * rho_floor), rb = fmax(r1, 0.5 * rho_floor);
+        const double saa = fma(gax, gax, fma(gay, gay, gaz * gaz)) + 1.0e-40;
+        const double sbb = fma(gbx, gbx, fma(gby, gby, gbz * gbz)) + 1.0e-40;
+        const double sab = fma(gax, gbx, fma(gay, gby, gaz * gbz));
+        const double ax = CODE == NBX_XC_TPSS ? 1.0 : 0.9;
+        XcDer o = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        double vta = 0.0, vtb = 0.0;
+        xc_tpss_x(ax, ra, saa, ta, o.e, o.va, o.vaa, vta);
+        xc_tpss_x(ax, rb, sbb, tb, o.e, o.vb, o.vbb, vtb);
+        double ec, dc[6];
+        xc_tpss_c(ra, rb, saa, sab, sbb, ta + tb, ec, dc);
+        o.e += ec, o.va += dc[0], o.vb += dc[1], o.vaa += dc[2], o.vab += dc[3], o.vbb += dc[4];
+        vta += dc[5], vtb += dc[5];
+        const double wk = wg * keep;
+        e_w = wk * o.e;
+        vr[g] = wk * o.va;
+        vr[npts + g] = wk * o.vb;
+        vt[g] = wk * vta;
+        vt[npts + g] = wk * vtb;
+        const double a2 = 2.0 * wk * o.vaa, b2 = 2.0 * wk * o.vbb, ab = wk * o.vab;
+        vec[g] = fma(a2, gax, ab * gbx);
+        vec[npts + g] = fma(a2, gay, ab * gby);
+        vec[2 * npts + g] = fma(a2, gaz, ab * gbz);
+        vec[3 * npts + g] = fma(b2, gbx, ab * gax);
+        vec[4 * npts + g] = fma(b2, gby, ab * gay);
+        vec[5 * npts + g] = fma(b2, gbz, ab * gaz);
+    }
+    const double es = nbx_block_sum(e_w, red);
+    const double ns = nbx_block_sum(n_w, red);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = es;
+        part[2 * blockIdx.x + 1] = ns;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ potential pass with tau
+// xc_vmat_kernel with four products per step of 16 grid points, all into the same accumulators: A = ao against
+// B = half (xc_vmat_kernel's step, unchanged), then A = dao_a against B = 1/4 vt dao_a for a = x, y, z, each B built on
+// the fly.  The (step, operand) pairs run through the same double-buffered LDS tile as one sequence four times as long:
+// no more LDS, one barrier per product.  With vt = 0 the three extra products add zeros: xc_vmat_kernel's bits.
+template <int BT>
+__global__ __launch_bounds__(64 * BT) void xc_vmat_tau_kernel(int64_t npts, int nao, int64_t chunk, int nblk,
+                                                              const double* __restrict__ ao, const double* __restrict__ dao,
+                                                              const double* __restrict__ vr, const double* __restrict__ vec,
+                                                              const double* __restrict__ vt, double* __restrict__ part) {
+    constexpr int W = 16 * BT, LD = (W % 32 == 16) ? W : W + 16, NT = 64 * BT;
+    __shared__ __attribute__((aligned(16))) double hs[2][16 * LD];
+    const int x = blockIdx.z;
+    const int bm = blockIdx.y / nblk, bn = blockIdx.y - bm * nblk;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fk = lane >> 4;
+    const int64_t g_begin = (int64_t)blockIdx.x * chunk, g_end = min(npts, g_begin + chunk);
+    const int64_t plane = npts * (int64_t)nao;
+    const double* vrx = vr + (int64_t)x * npts;
+    const double* vcx = vec + (int64_t)(3 * x) * npts;
+    const double* vtx = vt + (int64_t)x * npts;
+    const int m = W * bm + 16 * wave + fr;  // the A-fragment column of ao / dao_a (row of the result) of this lane
+    const bool m_ok = m < nao;
+    xc_v4 acc[BT];
+#pragma unroll
+    for (int c = 0; c < BT; ++c) acc[c] = (xc_v4){0.0, 0.0, 0.0, 0.0};
+
+    auto produce = [&](int buf, int64_t g0, int op) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {  // 16 W elements over NT = 4 W threads
+            const int e = threadIdx.x + i * NT;
+            const int gl = e / W, nl = e - gl * W;
+            const int64_t g = g0 + gl;
+            const int n = W * bn + nl;
+            double h = 0.0;
+            if (g < g_end && n < nao) {
+                const int64_t off = g * nao + n;
+                if (op == 0)
+                    h = fma(0.5 * vrx[g], ao[off],
+                            fma(vcx[g], dao[off], fma(vcx[npts + g], dao[plane + off], vcx[2 * npts + g] * dao[2 * plane + off])));
+                else
+                    h = 0.25 * vtx[g] * dao[(op - 1) * plane + off];
+            }
+            hs[buf][gl * LD + nl] = h;
+        }
+    };
+
+    int buf = 0;
+    const int64_t nseq = g_begin < g_end ? 4 * ((g_end - g_begin + 15) / 16) : 0;  // (step, operand) pairs
+    if (nseq > 0) produce(0, g_begin, 0);
+    for (int64_t it = 0; it < nseq; ++it) {
+        const int64_t g0 = g_begin + 16 * (it >> 2);
+        const int op = (int)(it & 3);
+        __syncthreads();  // hs[buf] is complete; hs[buf ^ 1] has been consumed
+        if (it + 1 < nseq) produce(buf ^ 1, g_begin + 16 * ((it + 1) >> 2), (int)((it + 1) & 3));
+        const double* src = op == 0 ? ao : dao + (op - 1) * plane;
+        double a[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const int64_t g = g0 + 4 * kk + fk;
+            a[kk] = (m_ok && g < g_end) ? src[g * nao + m] : 0.0;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int c = 0; c < BT; ++c)
+                acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], hs[buf][(4 * kk + fk) * LD + 16 * c + fr], acc[c], 0, 0, 0);
+        buf ^= 1;
+    }
+    // this chunk's contribution to the block: part[chunk][x][row][col]
+    double* out = part + ((int64_t)blockIdx.x * 2 + x) * (int64_t)nao * nao;
+#pragma unroll
+    for (int c = 0; c < BT; ++c) {
+        const int col = W * bn + 16 * c + fr;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = W * bm + 16 * wave + fk + 4 * r;
+            if (row < nao && col < nao) out[(int64_t)row * nao + col] = acc[c][r];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int nbx_xc_rho_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
+                              const double* d_dm, double* d_rho, double* d_grad, double* d_tau) {
+    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_dm && d_rho && d_grad && d_tau && npts >= 0 && nao >= 1);
+    const int64_t kp = (nao + 3) & ~3ll;
+    const size_t lds = (size_t)(2 * kp * 16) * sizeof(double);
+    if (lds > 160 * 1024) {
+        nbx_set_error("nbx_xc_rho_tau: nao = %lld beyond the LDS-resident density slab (limit 640)", (long long)nao);
+        return NBX_E_UNSUPPORTED;
+    }
+    if (npts == 0) return NBX_OK;
+    const dim3 grid((unsigned)nbx_cdiv(npts, 64));
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xc_rho_tau_kernel<40>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xc_rho_tau_kernel<0>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    if (kp <= 160)
+        hipLaunchKernelGGL(xc_rho_tau_kernel<40>, grid, dim3(256), lds, ctx->stream, npts, (int)nao, d_ao, d_dao, d_dm, d_rho,
+                           d_grad, d_tau);
+    else
+        hipLaunchKernelGGL(xc_rho_tau_kernel<0>, grid, dim3(256), lds, ctx->stream, npts, (int)nao, d_ao, d_dao, d_dm, d_rho,
+                           d_grad, d_tau);
+    NBX_LAUNCH_CHECK();
+    return NBX_OK;
+}
+
+extern "C" int nbx_xc_functional_mgga(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
+                                      const double* d_tau, const double* d_w, double rho_floor, double* d_vr, double* d_vec,
+                                      double* d_vt, double* d_sums, void* d_work, size_t work_bytes) {
+    NBX_CHECK_ARG(code == NBX_XC_TPSS || code == NBX_XC_TPSSH);
+    NBX_CHECK_ARG(ctx && d_rho && d_grad && d_tau && d_w && d_vr && d_vec && d_vt && d_sums && d_work && npts >= 0);
+    NBX_CHECK_ARG(rho_floor > 0.0 && work_bytes >= nbx_xc_functional_worksize(npts));
+    if (npts == 0) return nbx_memset(ctx, d_sums, 0, 2 * sizeof(double));
+    const int64_t nblk = nbx_cdiv(npts, XC_FN_THREADS);
+    NBX_CHECK_ARG(nblk < (1ll << 30));
+    double* part = static_cast<double*>(d_work);
+    if (code == NBX_XC_TPSS)
+        hipLaunchKernelGGL(xc_functional_mgga_kernel<NBX_XC_TPSS>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,
+                           d_rho, d_grad, d_tau, d_w, rho_floor, d_vr, d_vec, d_vt, part);
+    else
+        hipLaunchKernelGGL(xc_functional_mgga_kernel<NBX_XC_TPSSH>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,
+                           d_rho, d_grad, d_tau, d_w, rho_floor, d_vr, d_vec, d_vt, part);
+    NBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(xc_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, (int)nblk, part, d_sums);
+    NBX_LAUNCH_CHECK();
+    return NBX_OK;
+}
+
+extern "C" size_t nbx_xc_vmat_tau_worksize(int64_t npts, int64_t nao) { return nbx_xc_vmat_worksize(npts, nao); }
+
+extern "C" int nbx_xc_vmat_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
+                               const double* d_vr, const double* d_vec, const double* d_vt, double* d_vxc, void* d_work,
+                               size_t work_bytes) {
+    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_vr && d_vec && d_vt && d_vxc && npts >= 0 && nao >= 1 && nao <= (1 << 15));
+    const int64_t n2 = nao * nao;
+    if (npts == 0) return nbx_memset(ctx, d_vxc, 0, (size_t)(2 * n2) * sizeof(double));
+    NBX_CHECK_ARG(d_work && work_bytes >= nbx_xc_vmat_tau_worksize(npts, nao));
+    const int bt = vmat_bt(nao);
+    const int64_t chunk = vmat_chunk(npts, nao), nchunk = nbx_cdiv(npts, chunk), nblk = nbx_cdiv(nao, 16 * bt);
+    NBX_CHECK_ARG(nblk * nblk <= 65535 && nchunk < (1ll << 31));
+    double* part = static_cast<double*>(d_work);
+    const dim3 grid((unsigned)nchunk, (unsigned)(nblk * nblk), 2);
+#define NBX_VMAT_TAU(BT_)                                                                                                  \
+    hipLaunchKernelGGL(xc_vmat_tau_kernel<BT_>, grid, dim3(64 * BT_), 0, ctx->stream, npts, (int)nao, chunk, (int)nblk, d_ao, \
+                       d_dao, d_vr, d_vec, d_vt, part)
+    switch (bt) {
+        case 1: NBX_VMAT_TAU(1); break;
+        case 2: NBX_VMAT_TAU(2); break;
+        case 3: NBX_VMAT_TAU(3); break;
+        case 4: NBX_VMAT_TAU(4); break;
+        default: NBX_VMAT_TAU(5); break;
+    }
+#undef NBX_VMAT_TAU
+    NBX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(xc_vmat_reduce_kernel, dim3((unsigned)nbx_cdiv(2 * n2, 256)), dim3(256), 0, ctx->stream, (int)nao,
+                       (int)nchunk, part, d_vxc);
+    NBX_LAUNCH_CHECK();
+    return NBX_OK;
+}

@@ -163,7 +163,8 @@ class BuiltinHFProvider:
     cover: molecules of H, C, N, O (F) in STO-3G, 6-31G, 6-31G* or cc-pVDZ with ``xc_functional`` = 'b3lyp' (the reference's
     default workflow: global B3LYP Kohn-Sham, nbed/driver.py:155-191), 'b3lyp5', 'blyp', 'pbe', 'pbeh' / 'pbe1pbe'
     (the functional also called PBE0; that spelling is not accepted), 'lda', 'lda,vwn', 'lda,pw_mod' or 'hf' (exact
-    exchange: HF-in-HF embedding) -- the names of ``nbed_amd.xc.HYBRID_FRACTION``; PySCF's ``dft.UKS`` accepts the same
+    exchange: HF-in-HF embedding) -- the names of ``nbed_amd.xc.HYBRID_FRACTION`` -- the range-separated 'cam-b3lyp' and
+    'lc-blyp' (``RSH_PARAMETERS``) or the meta-GGAs 'tpss' and 'tpssh' (``MGGA_PARAMETERS``); PySCF's ``dft.UKS`` accepts the same
     strings.  One-electron integrals come from the
     host-side McMurchie-Davidson engine, (pq|rs) from it or from the same scheme on the device (``eri_engine``),
     exchange-correlation from the host-side quadrature
@@ -215,7 +216,7 @@ class BuiltinHFProvider:
         from . import xc as xcmod
 
         name = str(config.xc_functional).lower().replace(" ", "")
-        return ((name in xcmod.HYBRID_FRACTION or name in xcmod.RSH_PARAMETERS)
+        return ((name in xcmod.HYBRID_FRACTION or name in xcmod.RSH_PARAMETERS or name in xcmod.MGGA_PARAMETERS)
                 and integrals.supports(config.geometry, str(config.basis)))
 
     def _integrals(self, config: NbedConfig):
@@ -487,7 +488,7 @@ class BuiltinHFProvider:
             from . import xc as xcmod
 
             raise NbedDriverError(f"BuiltinHFProvider covers xc_functional in "
-                                  f"{sorted(xcmod.HYBRID_FRACTION) + sorted(xcmod.RSH_PARAMETERS)} ('pbeh' / "
+                                  f"{sorted(xcmod.HYBRID_FRACTION) + sorted(xcmod.RSH_PARAMETERS) + sorted(xcmod.MGGA_PARAMETERS)} ('pbeh' / "
                                   "'pbe1pbe' is the functional also called PBE0), H/C/N/O in STO-3G, 6-31G(*), cc-pVDZ")
         self._refuse_rsh_on_a_factor(config.xc_functional)
         hcore, energy_nuc = self._with_mm(config, run_qmmm, self._be)

@@ -30,9 +30,14 @@ Functionals (libxc definitions, spin-polarised):
                the scheme of Iikura, Tsuneda, Yanai and Hirao (J. Chem. Phys. 115, 3540 (2001)).  The parameters of these
                two are the papers': libxc is not installed here, so its HYB_GGA_XC_CAM_B3LYP / HYB_GGA_XC_LC_BLYP could not
                be compared (DESIGN.md section 17 lists the converged energies for someone who can).
+  * ``tpss``   the meta-GGA of Tao, Perdew, Staroverov and Scuseria (Phys. Rev. Lett. 91, 146401 (2003)): exchange and
+               correlation that also read the kinetic-energy density tau_s = 1/2 sum_i |grad psi_i|^2 (``energy_density_mgga``)
+  * ``tpssh``  0.9 TPSS exchange + TPSS correlation + 0.1 HF (Staroverov, Scuseria, Tao and Perdew, J. Chem. Phys. 119,
+               12129 (2003))
   * ``hf``     no semi-local part, 100 % exact exchange
 Energy densities are written once, in torch float64; their derivatives with respect to
-(rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb) come from autograd, not from hand-derived formulas.
+(rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb) -- and (tau_a, tau_b) for the meta-GGAs -- come from autograd, not from
+hand-derived formulas.
 
 Grid: Becke fuzzy cells (three smoothing iterations, Bragg-Slater size adjustment) over
 Gauss-Chebyshev radial shells (Becke's mapping r = R (1 + x) / (1 - x)) times a product angular rule
@@ -68,14 +73,21 @@ HYBRID_FRACTION = {"hf": 1.0, "b3lyp": 0.2, "lda": 0.0, "lda,vwn_rpa": 0.0, "lda
 RSH_PARAMETERS = {"cam-b3lyp": (0.33, 0.19, 0.46), "camb3lyp": (0.33, 0.19, 0.46), "lc-blyp": (0.33, 0.0, 1.0)}
 
 
+#: meta-GGAs (functions of tau as well): the fraction of exact exchange
+MGGA_PARAMETERS = {"tpss": 0.0, "tpssh": 0.1}
+
+
 def hybrid_fraction(xc: str) -> float:
     """The fraction of full-range exact exchange (alpha of ``rsh_parameters``; a range-separated hybrid adds
     beta K_lr(omega) to it)."""
     key = str(xc).lower().replace(" ", "")
     if key in RSH_PARAMETERS:
         return RSH_PARAMETERS[key][1]
+    if key in MGGA_PARAMETERS:
+        return MGGA_PARAMETERS[key]
     if key not in HYBRID_FRACTION:
-        raise ValueError(f"functional {xc!r} is not in nbed_amd.xc ({sorted(HYBRID_FRACTION) + sorted(RSH_PARAMETERS)})")
+        raise ValueError(f"functional {xc!r} is not in nbed_amd.xc "
+                         f"({sorted(HYBRID_FRACTION) + sorted(RSH_PARAMETERS) + sorted(MGGA_PARAMETERS)})")
     return HYBRID_FRACTION[key]
 
 
@@ -583,6 +595,115 @@ def _pbe_c(t, ra, rb, saa, sab, sbb):
     return rho * (eps + g3 * t.log1p(em * frac))
 
 
+# Meta-GGA conventions (stated here once; csrc/xc.hip and tests/xc_mgga_reference.py copy them).  The callers hand over
+# densities clamped at RHO_FLOOR / 2 and sigma_aa, sigma_bb lifted by 1e-40, as for the GGAs.  Wherever z = tau_W / tau is
+# formed, tau is clamped from below at the tau_W = sigma / (8 n) of the same quantities (on a finite basis and grid
+# tau < tau_W does occur): the test is ``tau >= sigma / (8 n) * TPSS_CLAMP`` in float64 as written, and where it fails
+# z = 1 and alpha = 0 are constants (their derivatives vanish).  TPSS_CLAMP = 1 - 1e-10, not 1: the potential has a kink
+# at the clamp (dz and dalpha jump to 0), and a one-orbital density -- the hydrogen atom -- has tau = tau_W at EVERY
+# point, up to the rounding of the density pass; with the test at 1 each point would take its side of the kink by that
+# rounding and v_xc would differ by 1e-3 between two correct evaluations.  So z <= 1 + 1e-10, not z <= 1.
+# "The larger of" is where(a >= b, a, b).  Exchange clamps each channel's tau against that channel's tau_W; correlation
+# clamps tau_a + tau_b against the total tau_W.
+TPSS_CLAMP = 1.0 - 1e-10
+_TPSS_KAPPA, _TPSS_B, _TPSS_C, _TPSS_E, _TPSS_MU, _TPSS_D = 0.804, 0.40, 1.59096, 1.537, 0.21951, 2.8
+
+
+def _tpss_x(t, ra, rb, saa, sbb, ta, tb):
+    """TPSS exchange, spin-scaled: per channel e = -cx rho^(4/3) F_x(p, z) (E_x[n_a, n_b] = 1/2 E_x[2 n_a] + 1/2 E_x[2 n_b],
+    tau doubled too), with p = sigma / (4 (6 pi^2)^(2/3) rho^(8/3)), z = sigma / (8 rho tau) and
+    alpha = (5p/3)(1/z - 1) = (tau - tau_W) / (cF rho^(5/3)), cF = (3/10)(6 pi^2)^(2/3) -- the second form: at a vanishing
+    gradient the first is 0 x inf."""
+    cx = 1.5 * (3.0 / (4.0 * math.pi)) ** (1.0 / 3.0)
+    c2 = 0.25 / (6.0 * math.pi**2) ** (2.0 / 3.0)
+    cf = 0.3 * (6.0 * math.pi**2) ** (2.0 / 3.0)
+    kappa, b, c, e, mu = _TPSS_KAPPA, _TPSS_B, _TPSS_C, _TPSS_E, _TPSS_MU
+    se = math.sqrt(e)
+    out = 0.0
+    for r, s, tau in ((ra, saa, ta), (rb, sbb, tb)):
+        r13 = r ** (1.0 / 3.0)
+        r43, r53 = r13 * r, r13 * r13 * r
+        p = c2 * s / (r43 * r43)
+        tw = s / (8.0 * r)
+        ok = tau >= tw * TPSS_CLAMP
+        tsafe = t.where(ok, tau, t.ones_like(tau))
+        z = t.where(ok, tw / tsafe, t.ones_like(tau))
+        alpha = t.where(ok, (tsafe - tw) / (cf * r53), t.zeros_like(tau))
+        z2 = z * z
+        # (alpha - 1) / sqrt(1 + b alpha (alpha - 1)): differentiated as written, the two terms of its derivative cancel
+        # to 1 / alpha of their size (z = 1e-6: alpha = 1e6); from alpha = 2 on it is 1 / sqrt(v^2 + b v + b),
+        # v = 1 / (alpha - 1), whose derivative is a sum of like terms
+        far = alpha >= 2.0
+        near_alpha = t.where(far, t.zeros_like(alpha), alpha)
+        v = 1.0 / t.where(far, alpha - 1.0, t.ones_like(alpha))
+        ratio = t.where(far, 1.0 / t.sqrt(v * v + b * v + b),
+                        (near_alpha - 1.0) / t.sqrt(1.0 + b * near_alpha * (near_alpha - 1.0)))
+        qb = 0.45 * ratio + 2.0 * p / 3.0
+        num = ((10.0 / 81.0 + c * z2 / (1.0 + z2) ** 2) * p + 146.0 / 2025.0 * qb * qb
+               - 73.0 / 405.0 * qb * t.sqrt(0.18 * z2 + 0.5 * p * p) + (10.0 / 81.0) ** 2 / kappa * p * p
+               + 2.0 * se * (10.0 / 81.0) * 0.36 * z2 + e * mu * p * p * p)
+        x = num / (1.0 + se * p) ** 2
+        out = out - cx * r43 * (1.0 + kappa * x / (kappa + x))  # 1 + kappa - kappa / (1 + x / kappa)
+    return out
+
+
+def _pbe_c_eps_polarised(t, r, s):
+    """eps_PBE(n_s, 0, grad n_s, 0) per electron: ``_pbe_c`` at zeta = 1 written without the empty channel (f(zeta) = 1,
+    zeta^4 = 1, 1 - zeta^4 = 0: eps_PW = eps_1; phi = 2^(-1/3)), so that nothing is differentiated with respect to it."""
+    x = ((3.0 / (4.0 * math.pi)) / r) ** (1.0 / 6.0)
+    a, a1, b1, b2, b3, b4 = 0.01554535, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517
+    eps = -2.0 * a * (1.0 + a1 * x * x) * t.log1p(1.0 / (2.0 * a * x * (b1 + x * (b2 + x * (b3 + x * b4)))))
+    bg = _PBE_BETA / _PBE_GAMMA
+    g3 = 0.5 * _PBE_GAMMA  # gamma phi^3
+    ct = math.pi / (16.0 * (3.0 * math.pi**2) ** (1.0 / 3.0))
+    tt = ct * s / (2.0 ** (-2.0 / 3.0) * r ** (7.0 / 3.0))
+    em = t.expm1(-eps / g3)
+    y = bg * tt / em
+    den = 1.0 + y + y * y
+    frac = t.where(y > 1.0, 1.0 - 1.0 / den, (y + y * y) / den)
+    return eps + g3 * t.log1p(em * frac)
+
+
+def _tpss_c(t, ra, rb, saa, sab, sbb, ta, tb):
+    """TPSS correlation e = n eps_revPKZB (1 + d eps_revPKZB z^3),
+    eps_revPKZB = eps_PBE (1 + C z^2) - (1 + C) z^2 sum_s (n_s / n) max(eps_PBE(n_s, 0, grad n_s, 0), eps_PBE),
+    C = (0.53 + 0.87 zeta^2 + 0.50 zeta^4 + 2.26 zeta^6) / (1 + xi^2 ((1 + zeta)^(-4/3) + (1 - zeta)^(-4/3)) / 2)^4.
+    xi^2 ((1 +- zeta)^(-4/3)) is formed from 1 +- zeta = 2 n_s / n (never by subtraction) and C as the fourth power of
+    1 / (1 + ...): at a fully polarised point with a gradient of zeta the bracket is 1e18 and C underflows towards 0 with
+    finite derivatives."""
+    rho = ra + rb
+    st = saa + 2.0 * sab + sbb
+    tau = ta + tb
+    tw = st / (8.0 * rho)
+    ok = tau >= tw * TPSS_CLAMP
+    z = t.where(ok, tw / t.where(ok, tau, t.ones_like(tau)), t.ones_like(tau))
+    z2 = z * z
+    eps = _pbe_c(t, ra, rb, saa, sab, sbb) / rho
+    ea, eb = _pbe_c_eps_polarised(t, ra, saa), _pbe_c_eps_polarised(t, rb, sbb)
+    ea, eb = t.where(ea >= eps, ea, eps), t.where(eb >= eps, eb, eps)
+    zeta = (ra - rb) / rho
+    up, dn = 2.0 * ra / rho, 2.0 * rb / rho
+    zz = zeta * zeta
+    num = 0.53 + zz * (0.87 + zz * (0.50 + zz * 2.26))
+    q = rb * rb * saa - 2.0 * ra * rb * sab + ra * ra * sbb  # n^4 |grad zeta|^2 / 4
+    xh = q * (up ** (-4.0 / 3.0) + dn ** (-4.0 / 3.0)) / (2.0 * (3.0 * math.pi**2) ** (2.0 / 3.0) * rho ** (14.0 / 3.0))
+    inv = 1.0 / (1.0 + xh)
+    big_c = num * (inv * inv) * (inv * inv)
+    rev = eps * (1.0 + big_c * z2) - (1.0 + big_c) * z2 * (ra / rho * ea + rb / rho * eb)
+    return rho * rev * (1.0 + _TPSS_D * rev * z2 * z)
+
+
+def energy_density_mgga(xc: str, ra, rb, saa, sab, sbb, ta, tb):
+    """Semi-local exchange-correlation energy per volume of a meta-GGA (``MGGA_PARAMETERS``): torch tensors of the spin
+    densities, the sigmas and the kinetic-energy densities tau_s = 1/2 sum_i |grad psi_i|^2."""
+    t = _torch()
+    key = str(xc).lower().replace(" ", "")
+    if key not in MGGA_PARAMETERS:
+        raise ValueError(f"functional {xc!r} is not a meta-GGA of nbed_amd.xc ({sorted(MGGA_PARAMETERS)})")
+    return ((1.0 - MGGA_PARAMETERS[key]) * _tpss_x(t, ra, rb, saa, sbb, ta, tb)
+            + _tpss_c(t, ra, rb, saa, sab, sbb, ta, tb))
+
+
 def energy_density(xc: str, ra, rb, saa, sab, sbb, omega: float | None = None):
     """Semi-local exchange-correlation energy per volume (torch tensors); None for ``hf``.  ``omega``: another range
     separation than the functional's own (range-separated hybrids only)."""
@@ -590,6 +711,8 @@ def energy_density(xc: str, ra, rb, saa, sab, sbb, omega: float | None = None):
     key = str(xc).lower().replace(" ", "")
     if key == "hf":
         return None
+    if key in MGGA_PARAMETERS:
+        raise ValueError(f"functional {xc!r} is a meta-GGA: it needs tau (energy_density_mgga)")
     if key in RSH_PARAMETERS:
         w, alpha, beta = RSH_PARAMETERS[key]
         w = w if omega is None else float(omega)
@@ -681,9 +804,18 @@ class XCProvider:
         nbx_xc_functional (analytic energy density and derivatives, weights folded in, E_xc reduced on the device),
         nbx_xc_vmat (the potential matrix with its ``half`` factor built on the fly).  Three kernels and two small
         reductions per evaluation; the host sees E_xc, the electron count and the (2, nao, nao) result."""
-        from ._nbx import XC_CODES, XC_RS_CODES
+        from ._nbx import XC_CODES, XC_MGGA_CODES, XC_RS_CODES
 
         dmd = be.asarray(0.5 * (dm + dm.transpose(0, 2, 1)))
+        if self.xc in XC_MGGA_CODES:
+            # the meta-GGA chain: nbx_xc_rho_tau adds tau = 1/2 sum_a diag(dao_a D dao_a^T) to the density pass,
+            # nbx_xc_functional_mgga returns w dE/dtau as well, nbx_xc_vmat_tau adds 1/4 v_tau dao_a to the operand
+            rho, grad, tau = be.xc_rho_tau(self._ao, self._dao, dmd)
+            vr, vec, vt, sums = be.xc_functional_mgga(XC_MGGA_CODES[self.xc], rho, grad, tau, self._w, self.RHO_FLOOR)
+            vxc = be.xc_vmat_tau(self._ao, self._dao, vr, vec, vt)
+            sums_h = be.to_host(sums)
+            self.nelec_last = float(sums_h[1])
+            return float(sums_h[0]), be.to_host(vxc)
         rho, grad = be.xc_rho(self._ao, self._dao, dmd)
         if self.xc in XC_RS_CODES:
             vr, vec, sums = be.xc_functional_rs(XC_RS_CODES[self.xc], self.omega, rho, grad, self._w, self.RHO_FLOOR)
@@ -704,12 +836,15 @@ class XCProvider:
         # host form (the CPU suite's checker; also the definition the HIP kernels are tested against)
         dmd = t.as_tensor(dm).to(self.device)
         dmd = 0.5 * (dmd + dmd.transpose(1, 2))
-        rho, grad = [[], []], [[], []]
+        mgga = self.xc in MGGA_PARAMETERS
+        rho, grad, tau = [[], []], [[], []], [[], []]
         for ao, dao in self._blocks:
             for x in range(2):
                 c = ao @ dmd[x]                                            # (g, nao)
                 rho[x].append((c * ao).sum(dim=1))
                 grad[x].append(2.0 * (dao * c[None]).sum(dim=2))           # D symmetric
+                if mgga:  # tau = 1/2 sum_a diag(dao_a D dao_a^T)
+                    tau[x].append(0.5 * sum(((dao[a] @ dmd[x]) * dao[a]).sum(dim=1) for a in range(3)))
         rho = [t.cat(r) for r in rho]
         ga, gb = (t.cat(g, dim=1) for g in grad)
         w = self._w
@@ -721,9 +856,17 @@ class XCProvider:
         saa = ((ga * ga).sum(dim=0) + tiny).requires_grad_(True)
         sab = (ga * gb).sum(dim=0).requires_grad_(True)
         sbb = ((gb * gb).sum(dim=0) + tiny).requires_grad_(True)
-        exc = (w * keep * energy_density(self.xc, ra, rb, saa, sab, sbb)).sum()
-        vra, vrb, vsaa, vsab, vsbb = (g if g is not None else t.zeros_like(w) for g in t.autograd.grad(
-            exc, (ra, rb, saa, sab, sbb), allow_unused=True))
+        vtau = None
+        if mgga:
+            ta, tb = (t.cat(x).requires_grad_(True) for x in tau)
+            exc = (w * keep * energy_density_mgga(self.xc, ra, rb, saa, sab, sbb, ta, tb)).sum()
+            vra, vrb, vsaa, vsab, vsbb, vta, vtb = (g if g is not None else t.zeros_like(w) for g in t.autograd.grad(
+                exc, (ra, rb, saa, sab, sbb, ta, tb), allow_unused=True))
+            vtau = (vta, vtb)
+        else:
+            exc = (w * keep * energy_density(self.xc, ra, rb, saa, sab, sbb)).sum()
+            vra, vrb, vsaa, vsab, vsbb = (g if g is not None else t.zeros_like(w) for g in t.autograd.grad(
+                exc, (ra, rb, saa, sab, sbb), allow_unused=True))
         # autograd differentiated sum_g w_g e_g: the derivatives already carry the weights
         vxc = t.zeros_like(dmd)
         for x, (vr, vs_same, gs, go) in enumerate(((vra, vsaa, ga, gb), (vrb, vsbb, gb, ga))):
@@ -736,6 +879,10 @@ class XCProvider:
                 half = 0.5 * vr[g0:g1, None] * ao + (vec[:, g0:g1, None] * dao).sum(dim=0)
                 n = ao.shape[1]  # K = grid points is long and M = N = nao short: split K, batch, sum
                 vxc[x] += (ao.view(-1, self.SPLIT, n).transpose(1, 2) @ half.view(-1, self.SPLIT, n)).sum(dim=0)
+                if vtau is not None:  # after V + V^T: 1/2 int v_tau grad phi_m . grad phi_n
+                    for a in range(3):
+                        quarter = 0.25 * vtau[x][g0:g1, None] * dao[a]
+                        vxc[x] += (dao[a].view(-1, self.SPLIT, n).transpose(1, 2) @ quarter.view(-1, self.SPLIT, n)).sum(dim=0)
                 g0 = g1
         vxc = vxc + vxc.transpose(1, 2)
         return float(exc.detach()), vxc.cpu().numpy()
