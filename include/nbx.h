@@ -1080,6 +1080,23 @@ int nbx_fci_diag(nbx_ctx* ctx, int64_t n, int64_t n_alpha_str, int64_t n_beta_st
 int nbx_fci_precond(nbx_ctx* ctx, int64_t ndet, double theta, double guard, const double* d_r, const double* d_diag,
                     double* d_out);
 
+/* Densities (csrc/fci_rdm.hip): what PySCF's make_rdm1 / make_rdm12 / trans_rdm12 give the reference's users from the
+ * fci.FCI object.  Between a bra b and a ket c of one sector, in the blocks and index order of d_two_body:
+ *      dm1[s][p,q] = <b| a+_ps a_qs |c>,   dm2[x][p,q,r,s] = <b| a+_ps a+_qt a_rt a_ss |c>,  (s,t) = aa, bb, ab.
+ * With D_x = nbx_fci_gather of x, Graw = D_b . D_c^T (nbx_gemm 'N','T') holds <b| E^s_lk E^t_mn |c> at
+ * [(s,kl),(t,mn)], <b| E^s_lk |c> in its last column and <b|c> in its corner.
+ *
+ * d_graw (slabs, 2n^2 + 1, 2n^2 + 1): partial products over disjoint ranges of determinants; they are added in
+ * ascending slab order, mapped to d_dm1 (2,n,n) and d_dm2 (3,n,n,n,n) with the delta_st delta_qs <b| E^s_pr |c>
+ * subtracted, and <b|c> goes to d_overlap[0].  One thread per output element, every element written.           */
+int nbx_fci_rdm_finish(nbx_ctx* ctx, int64_t n, int64_t slabs, const double* d_graw, double* d_dm1, double* d_dm2,
+                       double* d_overlap);
+/* d_dm1 (2,n,n) alone, without D: d_partial (n_alpha_str, 2n^2) receives <b| E_g |c> restricted to the bra's alpha
+ * row Ia (one workgroup per row, one wavefront per generator, the ket row staged in LDS: n_beta_str <= 13312), a
+ * second kernel sums it over Ia in ascending order.  d_bra may be d_ket.  No atomics: the same bits every time. */
+int nbx_fci_rdm1(nbx_ctx* ctx, int64_t n, int64_t n_alpha_str, int64_t n_beta_str, const int* d_link_a,
+                 const int* d_link_bt, const double* d_bra, const double* d_ket, double* d_partial, double* d_dm1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,8 @@ SIGNATURES = {
     "nbx_fci_scatter": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_double, _P, c_int, _P]),
     "nbx_fci_diag": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_double, _P]),
     "nbx_fci_precond": (c_int, [_P, c_int64, c_double, c_double, _P, _P, _P]),
+    "nbx_fci_rdm_finish": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
+    "nbx_fci_rdm1": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1834,6 +1834,25 @@ class HipBackend:
         self._call("nbx_fci_precond", int(r.numel()), float(theta), float(guard), self._p(r), self._p(diag), self._p(out))
         return out
 
+    def fci_rdm_finish(self, n: int, slabs: int, graw):
+        """(dm1 (2,n,n), dm2 (3,n,n,n,n), overlap (1,)) from the ``slabs`` partial products D_b D_c^T (include/nbx.h,
+        "full CI", densities)."""
+        g1 = 2 * n * n + 1
+        if graw.numel() != slabs * g1 * g1:
+            raise ValueError("fci_rdm_finish: shape")
+        dm1, dm2, overlap = self.empty((2, n, n)), self.empty((3, n, n, n, n)), self.empty(1)
+        self._call("nbx_fci_rdm_finish", n, slabs, self._p(graw), self._p(dm1), self._p(dm2), self._p(overlap))
+        return dm1, dm2, overlap
+
+    def fci_rdm1(self, n: int, na_str: int, nb_str: int, link_a, link_bt, bra, ket, partial):
+        """dm1 (2,n,n) = <bra| a+_p a_q |ket> per spin without a D buffer; ``partial`` (na_str, 2n^2) is work space."""
+        if bra.numel() != na_str * nb_str or ket.numel() != na_str * nb_str or partial.numel() != na_str * 2 * n * n:
+            raise ValueError("fci_rdm1: shape")
+        dm1 = self.empty((2, n, n))
+        self._call("nbx_fci_rdm1", n, na_str, nb_str, self._p(link_a), self._p(link_bt), self._p(bra), self._p(ket),
+                   self._p(partial), self._p(dm1))
+        return dm1
+
     def fci(self, spatial, nelec, occupied=None, **kwargs):
         """Determinant FCI on the device (``nbed_amd.fci_gpu.solve_spatial``): the capability the driver asks for."""
         from . import fci_gpu

@@ -1026,6 +1026,7 @@ class NbedDriver:
             fci_emb = self._run_emb_fci(result["scf"])
             result["e_fci"] = fci_emb.e_tot + self.e_env + self.two_e_cross - corr
             result["fci_emb"] = fci_emb.e_tot - self.e_nuc
+            result["fci_solver"] = fci_emb  # the solver object itself: its density methods (rdm12, spin_square, ...)
         result["hf_emb"] = result["scf"].e_tot - self.e_nuc
         if cfg.run_dft_in_dft is True:
             result.update(self._dft_in_dft(projector))

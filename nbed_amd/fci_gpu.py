@@ -16,6 +16,9 @@ above: 10^6 - 10^7 determinants on the MI355X.
   gather D[g,K] = <K|E_g|c> -> E = [G | k] [D ; c] (matrix cores) -> sigma_I = const c_I + sum <I|E_g|K> E[g,K],
   the last a gather per output element in a fixed order: a sigma is bit-reproducible for a given plan.
 * K runs over chunks of whole alpha rows, so D and E never hold more determinants than the memory plan gives them.
+* The same gather gives the densities: D_b D_c^T holds <b| E_g E_g' |c>, <b| E_g |c> and <b|c>, and an index map makes
+  the spin-resolved 1- and 2-particle (transition) density matrices of it (``RdmBuilder``, ``rdm1``, ``rdm12`` and the
+  methods of ``FCIGpuResult``; csrc/fci_rdm.hip).
 
 A start vector of pure spin symmetry keeps the iteration in that symmetry when the integrals are spin-restricted, as
 PySCF's solver does: from a closed-shell determinant the result is the lowest SINGLET, even where a state of another
@@ -38,6 +41,7 @@ from .exceptions import NbedDriverError
 DEVICE_BYTES = 288 * 10**9  # HBM of one MI355X: what memory_plan sizes the chunks for when nothing else is given
 MAX_SPACE = 16              # nbx_lincomb / nbx_dots take up to 16 vectors
 MAX_ROW = 13 * 1024         # beta strings in a row the kernels stage in LDS (csrc/fci.hip)
+COMPUTE_UNITS = 256         # of one MI355X: what default_slabs fills
 
 
 # ---------------------------------------------------------------- strings and link tables (host, a few MB)
@@ -130,6 +134,58 @@ def memory_plan(n: int, na: int, nb: int, space: int = 12, chunk_rows: int | Non
     return plan
 
 
+def default_slabs(n: int) -> int:
+    """Partial matrices the D_b D_c^T of the densities is split into: the output is (2n^2 + 1)^2, a few 128 x 128 tiles
+    at most, and the reduction runs over up to 2^31 determinants -- enough slabs that the batched GEMM launches at
+    least one workgroup per compute unit whichever tile ``nbx_gemm`` picks (128 is its largest)."""
+    tiles = (-(-(2 * n * n + 1) // 128)) ** 2
+    return -(-COMPUTE_UNITS // tiles)
+
+
+def memory_plan_rdm(n: int, na: int, nb: int, transition: bool = False, chunk_rows: int | None = None,
+                    slabs: int | None = None, direct_only: bool = False, capacity: int = DEVICE_BYTES) -> dict:
+    """Bytes the densities need, by group, computed before anything is allocated (host arithmetic):
+
+    vectors        the ket, and the bra of a transition density
+    tables         the two link tables (int32)
+    direct         the (Na, 2n^2) partials of the 1-RDM kernel
+    output         dm1, dm2 and the overlap
+    slab_partials  ``slabs`` matrices (2n^2 + 1)^2 that the split reduction accumulates into   } not with
+    d              D (2n^2 + 1, K) of one chunk of K = chunk_rows x Nb determinants, twice for a  } ``direct_only``
+                   transition density
+
+    ``chunk_rows`` None: as many alpha rows as ``capacity`` (less a tenth) leaves room for, at least one and fewer
+    than 2^31 determinants (one GEMM extent).  ``slabs`` None: ``default_slabs(n)``."""
+    n_a, n_b = comb(n, na), comb(n, nb)
+    ndet = n_a * n_b
+    g1 = 2 * n * n + 1
+    nvec = 2 if transition else 1
+    slabs = default_slabs(n) if slabs is None else int(slabs)
+    if not 1 <= slabs <= 65535:
+        raise ValueError("slabs must lie in [1, 65535]")
+    plan = {
+        "vectors": 8 * nvec * ndet,
+        "tables": 4 * (n_a * n * n + n * n * n_b),
+        "direct": 8 * n_a * (g1 - 1),
+        "output": 8 * ((g1 - 1) + (0 if direct_only else 3 * n**4 + 1)),
+        "slab_partials": 0 if direct_only else 8 * slabs * g1 * g1,
+    }
+    per_row = 8 * nvec * g1 * n_b
+    if chunk_rows is None:
+        room = int(0.9 * capacity) - sum(plan.values())
+        chunk_rows = max(1, min(n_a, room // per_row, (2**31 - 1) // n_b))
+    chunk_rows = int(chunk_rows)
+    if not 1 <= chunk_rows <= n_a:
+        raise ValueError(f"chunk_rows must lie in [1, {n_a}]")
+    plan["d"] = 0 if direct_only else per_row * chunk_rows
+    plan["total"] = sum(plan.values())
+    plan["chunk_rows"] = chunk_rows
+    plan["chunks"] = -(-n_a // chunk_rows)
+    plan["slabs"] = slabs
+    plan["ndet"] = ndet
+    return plan
+
+
 def _device_backend(backend):
     if backend is None:
         from .backend import get_backend
@@ -148,6 +204,12 @@ def _unpack(spatial):
 
 def _diagonal(be, n, str_a, str_b, one, two, constant):
     return be.fci_diag(n, be.int_array(str_a), be.int_array(str_b), one, two, float(constant))
+
+
+def _tables(be, n, na, nb):
+    """String masks (host) and the link tables as the kernels read them (device): alpha (Na, n^2), beta transposed
+    (n^2, Nb).  One construction for the sigma build and the densities."""
+    return strings(n, na), strings(n, nb), be.int_array(link_table(n, na)), be.int_array(link_table(n, nb).T)
 
 
 class SigmaBuilder:
@@ -176,9 +238,7 @@ class SigmaBuilder:
                 f"{self.plan['chunk_rows']} alpha rows, {self.plan['tables']} of tables); {free} are free")
         self.rows = self.plan["chunk_rows"]
         self.one, self.two = be.asarray(one), be.asarray(two)
-        self.str_a, self.str_b = strings(n, na), strings(n, nb)
-        self.link_a = be.int_array(link_table(n, na))
-        self.link_bt = be.int_array(link_table(n, nb).T)
+        self.str_a, self.str_b, self.link_a, self.link_bt = _tables(be, n, na, nb)
         self.g = be.fci_gmat(self.one, self.two)
         g = 2 * n * n
         self.d = be.empty((g + 1) * self.rows * self.n_b)
@@ -231,12 +291,175 @@ def diagonal(spatial, nelec, backend=None):
     return _diagonal(be, n, strings(n, int(nelec[0])), strings(n, int(nelec[1])), be.asarray(one), be.asarray(two), constant)
 
 
+# ---------------------------------------------------------------- densities
+# Between a bra b and a ket c of one sector (a state density is b = c), in the blocks and index order of
+# SpatialHamiltonian:  dm1[s][p,q] = <b| a+_ps a_qs |c>,  dm2[x][p,q,r,s] = <b| a+_ps a+_qt a_rt a_ss |c> for
+# (s,t) = aa, bb, ab; the ba block is dm2[2][q,p,s,r].  With D_x = fci_gather(x) (x itself in the last row)
+#     Graw = D_b D_c^T:  Graw[(s,kl),(t,mn)] = <b| E^s_lk E^t_mn |c>,  Graw[(s,kl), last] = <b| E^s_lk |c>,
+# and a+_ps a+_qt a_rt a_ss = E^s_ps E^t_qr - delta_st delta_qs E^s_pr is the index map of nbx_fci_rdm_finish.
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+class RdmBuilder:
+    """Densities of one (n_alpha, n_beta) sector: tables made once, buffers at the first use of each route.
+
+    ``rdm12``: per chunk of alpha rows a gather of the ket (and of the bra, if it is another vector), then
+    Graw += D_b D_c^T on the matrix cores, the reduction over the chunk's determinants cut into ``slabs`` contiguous
+    ranges that each add into a partial matrix of their own (one batched ``nbx_gemm``, the ragged last range a second
+    call); ``nbx_fci_rdm_finish`` adds the partials in a fixed order.  ``rdm1``: the direct kernel, no D.
+    ``transition``: plan for two D buffers; ``direct_only``: plan for none.  ``held``: bytes of the plan's vectors that
+    are on the device already."""
+
+    def __init__(self, be, n, nelec, chunk_rows: int | None = None, slabs: int | None = None, transition: bool = False,
+                 direct_only: bool = False, held: int = 0):
+        self.be = be
+        self.n = n = int(n)
+        self.na, self.nb = na, nb = int(nelec[0]), int(nelec[1])
+        if not (1 <= n <= 31 and 0 <= na <= n and 0 <= nb <= n):
+            raise ValueError(f"device FCI: 1 <= n <= 31 orbitals and 0 <= electrons per spin <= n expected (n = {n}, {nelec})")
+        self.n_a, self.n_b = comb(n, na), comb(n, nb)
+        self.ndet = self.n_a * self.n_b
+        if self.n_b > MAX_ROW:
+            raise NbedDriverError(f"device FCI: {self.n_b} beta strings per row exceed the {MAX_ROW} the kernels stage in LDS")
+        self.transition, self.direct_only = bool(transition), bool(direct_only)
+        self.plan = self._fit(self.transition, self.direct_only, chunk_rows, slabs, int(held))
+        self.rows, self.slabs = self.plan["chunk_rows"], self.plan["slabs"]
+        self.str_a, self.str_b, self.link_a, self.link_bt = _tables(be, n, na, nb)
+        self.d = [None, None]
+        self.graw = self.partial = None
+        self.seconds = None  # set to {"gather": 0.0, "gemm": 0.0, "finish": 0.0} to time the phases (synchronises)
+
+    def _fit(self, transition, direct_only, chunk_rows, slabs, held):
+        free = self.be.free_bytes()
+        plan = memory_plan_rdm(self.n, self.na, self.nb, transition, chunk_rows, slabs, direct_only, capacity=free + held)
+        if plan["total"] - held > free:
+            raise NbedDriverError(
+                f"densities of {self.n} orbitals with ({self.na}, {self.nb}) electrons, {self.ndet} determinants, need "
+                f"{plan['total'] - held} bytes of device memory ({plan['vectors']} of vectors, {plan['d']} for "
+                f"{2 if transition else 1} D of {plan['chunk_rows']} alpha rows, {plan['slab_partials']} for "
+                f"{plan['slabs']} slab partials, {plan['direct']} of 1-RDM partials, {plan['tables']} of tables, "
+                f"{plan['output']} of output); {free} are free")
+        return plan
+
+    def _vector(self, v, what):
+        shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+        if shape != (self.n_a, self.n_b) and shape != (self.ndet,):
+            raise ValueError(f"{what}: a vector of shape ({self.n_a}, {self.n_b}) expected, got {shape}")
+        return self.be.asarray(v).reshape(self.n_a, self.n_b)
+
+    def _pair(self, c, bra):
+        """(bra, ket) on the device; the bra IS the ket where none is given."""
+        ket = self._vector(c, "ket")
+        return (ket if bra is None or bra is c else self._vector(bra, "bra")), ket
+
+    def _timed(self, key, fn, *args):
+        if self.seconds is None:
+            return fn(*args)
+        self.be.synchronize()
+        t0 = time.perf_counter()
+        out = fn(*args)
+        self.be.synchronize()
+        self.seconds[key] += time.perf_counter() - t0
+        return out
+
+    def rdm1(self, c, bra=None):
+        """dm1 (2, n, n) on the device by the direct kernel."""
+        be = self.be
+        b, k = self._pair(c, bra)
+        if self.partial is None:
+            self.partial = be.empty((self.n_a, 2 * self.n * self.n))
+        return be.fci_rdm1(self.n, self.n_a, self.n_b, self.link_a, self.link_bt, b, k, self.partial)
+
+    def rdm12(self, c, bra=None):
+        """(dm1 (2,n,n), dm2 (3,n,n,n,n), overlap (1,)) on the device."""
+        be, n, g1 = self.be, self.n, 2 * self.n * self.n + 1
+        if self.direct_only:
+            raise NbedDriverError("this RdmBuilder was planned for the 1-RDM alone (direct_only)")
+        b, k = self._pair(c, bra)
+        two = b is not k
+        if two and not self.transition:  # a second D after all: the same chunks must still fit
+            there = (self.d[0], self.graw, self.partial)
+            held = 16 * self.ndet + self.plan["tables"] + sum(8 * t.numel() for t in there if t is not None)
+            self._fit(True, False, self.rows, self.slabs, held)
+            self.transition = True
+        if self.graw is None:
+            self.graw = be.zeros((self.slabs, g1, g1))
+        else:
+            self.graw.zero_()
+        for i in range(2 if two else 1):
+            if self.d[i] is None:
+                self.d[i] = be.empty(g1 * self.rows * self.n_b)
+        for row0 in range(0, self.n_a, self.rows):
+            rows = min(self.rows, self.n_a - row0)
+            cols = rows * self.n_b
+            dk = self.d[0][: g1 * cols]
+            self._timed("gather", be.fci_gather, n, self.n_a, self.n_b, row0, rows, self.link_a, self.link_bt, k, dk)
+            db = dk
+            if two:
+                db = self.d[1][: g1 * cols]
+                self._timed("gather", be.fci_gather, n, self.n_a, self.n_b, row0, rows, self.link_a, self.link_bt, b, db)
+            self._timed("gemm", self._accumulate, db, dk, cols)
+        return self._timed("finish", be.fci_rdm_finish, n, self.slabs, self.graw)
+
+    def _accumulate(self, db, dk, cols):
+        """graw[z] += D_b[:, slab z] D_c[:, slab z]^T.  Every partial starts from zero and is only ever added to, by
+        the chunks in ascending order: a fixed order of additions per element."""
+        be, g1 = self.be, 2 * self.n * self.n + 1
+        ks = -(-cols // self.slabs)
+        full = cols // ks
+        rem = cols - full * ks
+        be.gemm_raw("N", "T", g1, g1, ks, 1.0, db, cols, ks, dk, cols, ks, 1.0, self.graw, g1, g1 * g1, full)
+        if rem:
+            be.gemm_raw("N", "T", g1, g1, rem, 1.0, db[full * ks:], cols, 0, dk[full * ks:], cols, 0, 1.0, self.graw[full],
+                        g1, 0, 1)
+
+
+def _held(be, *vectors):
+    return sum(8 * v.numel() for v in vectors if v is not None and be.torch.is_tensor(v) and v.is_cuda)
+
+
+def rdm1(c, n, nelec, bra=None, backend=None):
+    """dm1 (2, n, n) = <bra| a+_ps a_qs |c> on the device by the direct kernel (no D buffer); ``c`` and ``bra`` are
+    host or device vectors (Na, Nb) in this module's determinant convention, ``bra`` None a state density."""
+    be = _device_backend(backend)
+    rb = RdmBuilder(be, n, nelec, transition=bra is not None and bra is not c, direct_only=True, held=_held(be, c, bra))
+    return rb.rdm1(c, bra)
+
+
+def rdm12(c, n, nelec, bra=None, backend=None, chunk_rows: int | None = None, slabs: int | None = None):
+    """(dm1 (2,n,n), dm2 (3,n,n,n,n)) on the device by gather, GEMM and finish."""
+    be = _device_backend(backend)
+    rb = RdmBuilder(be, n, nelec, chunk_rows, slabs, transition=bra is not None and bra is not c, held=_held(be, c, bra))
+    dm1, dm2, _ = rb.rdm12(c, bra)
+    return dm1, dm2
+
+
+def spin_square(dm2, nelec) -> float:
+    """<S^2> = S_z (S_z + 1) + n_beta - sum_pq dm2[ab][p,q,p,q] of a normalised state, S_z = (n_alpha - n_beta) / 2."""
+    na, nb = int(nelec[0]), int(nelec[1])
+    ab = _host(dm2[2])
+    sz = 0.5 * (na - nb)
+    return float(sz * (sz + 1.0) + nb - np.einsum("pqpq->", ab))
+
+
+def energy_from_rdm(spatial, dm1, dm2, overlap: float = 1.0) -> float:
+    """<b|H|c> = constant <b|c> + sum one_body dm1 + sum two_body[aa] dm2[aa] + sum two_body[bb] dm2[bb]
+    + 2 sum two_body[ab] dm2[ab] (host arithmetic on host copies)."""
+    constant, one, two = _unpack(spatial)
+    one, two, dm1, dm2 = _host(one), _host(two), _host(dm1), _host(dm2)
+    return float(float(constant) * float(overlap) + np.sum(one * dm1) + np.sum(two[0] * dm2[0]) + np.sum(two[1] * dm2[1])
+                 + 2.0 * np.sum(two[2] * dm2[2]))
+
+
 class FCIGpuResult:
     """Duck-types ``fci.FCIResult``: ``e_tot``, ``energies``, ``converged``, ``determinants``; ``ci`` (Na, Nb) -- for
-    nroots > 1 (nroots, Na, Nb) -- is copied to the host on first access."""
+    nroots > 1 (nroots, Na, Nb) -- is copied to the host on first access.  The density methods (``rdm1``, ``rdm12``,
+    ``trans_rdm1``, ``trans_rdm12``, ``spin_square``, ``natural_occupations``) return host arrays in the conventions
+    of ``rdm12`` above."""
 
     def __init__(self, be, energies, ci_dev, converged, iterations, residual_norm, strings_a, strings_b, n):
-        self._be, self._ci_dev, self._ci = be, ci_dev, None
+        self._be, self._ci_dev, self._ci, self._rdm = be, ci_dev, None, None
         self.energies = np.asarray(energies, dtype=float)
         self.e_tot = float(self.energies[0])
         self.converged = bool(converged)
@@ -259,6 +482,54 @@ class FCIGpuResult:
             return sum(((int(m) >> p) & 1) << (2 * p) for p in range(self.norb))
 
         return [spread(a) | (spread(b) << 1) for a in self.strings_a for b in self.strings_b]
+
+    # -- densities: the device copy of the vector while it exists, the host copy uploaded again once ``ci`` has dropped it
+    @property
+    def nelec(self):
+        return bin(int(self.strings_a[0])).count("1"), bin(int(self.strings_b[0])).count("1")
+
+    def _roots(self, i, j):
+        """Roots i and j as device vectors (Na, Nb); both are checked before anything is uploaded."""
+        nroots = int(self.energies.size)
+        for root in (i, j):
+            if not (isinstance(root, (int, np.integer)) and 0 <= root < nroots):
+                raise ValueError(f"root {root!r}: this result holds {nroots} root(s)")
+        v = self._ci_dev if self._ci_dev is not None else self._be.asarray(self._ci)
+        v = v.reshape(nroots, len(self.strings_a), len(self.strings_b))
+        return v[int(i)], v[int(j)]
+
+    def _builder(self):
+        if self._rdm is None:
+            held = 8 * len(self.strings_a) * len(self.strings_b) if self._ci_dev is not None else 0
+            self._rdm = RdmBuilder(self._be, self.norb, self.nelec, held=held)
+        return self._rdm
+
+    def trans_rdm12(self, i, j):
+        """(dm1, dm2) with dm1[s][p,q] = <i| a+_ps a_qs |j> between roots i and j, host arrays."""
+        bra, ket = self._roots(i, j)
+        dm1, dm2, _ = self._builder().rdm12(ket, None if i == j else bra)
+        return self._be.to_host(dm1), self._be.to_host(dm2)
+
+    def trans_rdm1(self, i, j):
+        bra, ket = self._roots(i, j)
+        return self._be.to_host(self._builder().rdm1(ket, None if i == j else bra))
+
+    def rdm1(self, root=0):
+        """dm1 (2, n, n) of a root by the direct kernel (no D buffer), a host array."""
+        return self.trans_rdm1(root, root)
+
+    def rdm12(self, root=0):
+        """(dm1 (2,n,n), dm2 (3,n,n,n,n)) of a root, host arrays."""
+        return self.trans_rdm12(root, root)
+
+    def spin_square(self, root=0) -> float:
+        return spin_square(self.rdm12(root)[1], self.nelec)
+
+    def natural_occupations(self, root=0) -> np.ndarray:
+        """Eigenvalues of dm1[alpha] + dm1[beta], descending."""
+        dm1 = self.rdm1(root)
+        total = dm1[0] + dm1[1]
+        return np.linalg.eigvalsh(0.5 * (total + total.T))[::-1].copy()
 
 
 def solve(constant, h1, h2, nelec, **kwargs) -> FCIGpuResult:

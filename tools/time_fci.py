@@ -2,7 +2,12 @@
 each phase, and Davidson iterations to convergence, for the global Hamiltonian of water / 6-31G (13 orbitals, (5, 5),
 1.66e6 determinants) and one larger synthetic sector (default n = 14, (6, 6), 9.0e6 determinants).
 
-    python tools/time_fci.py [n] [n_alpha] [n_beta] [chunk_rows]"""
+    python tools/time_fci.py [n] [n_alpha] [n_beta] [chunk_rows]
+
+With ``--rdm``: water / 6-31G only, medians of five after a warm-up, in one process: seconds per sigma (the yardstick),
+per ``rdm12`` split into gather / GEMM / finish, per direct ``rdm1``, and the GEMM with one slab against the default.
+
+    python tools/time_fci.py --rdm"""
 import sys
 import time
 from math import comb
@@ -18,10 +23,12 @@ from nbed_amd.backend import HipBackend  # noqa: E402
 from nbed_amd.driver import BuiltinHFProvider  # noqa: E402
 from nbed_amd.ham_builder import HamiltonianBuilder  # noqa: E402
 
-n_syn = int(sys.argv[1]) if len(sys.argv) > 1 else 14
-na_syn = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-nb_syn = int(sys.argv[3]) if len(sys.argv) > 3 else 6
-chunk_rows = int(sys.argv[4]) if len(sys.argv) > 4 else None
+RDM = "--rdm" in sys.argv
+args = [a for a in sys.argv[1:] if a != "--rdm"]
+n_syn = int(args[0]) if len(args) > 0 else 14
+na_syn = int(args[1]) if len(args) > 1 else 6
+nb_syn = int(args[2]) if len(args) > 2 else 6
+chunk_rows = int(args[3]) if len(args) > 3 else None
 WATER = "3\n\nO   0.0000  0.000  0.115\nH   0.0000  0.754  -0.459\nH   0.0000  -0.754  -0.459"
 
 be = HipBackend()
@@ -75,6 +82,54 @@ def time_solve(label, spatial, nelec, occupied, conv_tol):
     torch.cuda.empty_cache()
 
 
+def median_of_five(fn):
+    fn()  # (first launches, allocator)
+    be.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        fn()
+        be.synchronize()
+        times.append(time.perf_counter() - t0)
+    return float(np.median(times))
+
+
+def time_rdm(label, spatial, nelec):
+    sb = fci_gpu.SigmaBuilder(be, spatial, nelec, space=1, chunk_rows=chunk_rows)
+    n, ndet, g1 = sb.n, sb.ndet, 2 * sb.n * sb.n + 1
+    c = be.asarray(np.random.default_rng(0).standard_normal((sb.n_a, sb.n_b)))
+    c /= float(c.norm())
+    out = be.empty((sb.n_a, sb.n_b))
+    t_sigma = median_of_five(lambda: sb(c, out))
+    del sb, out
+    torch.cuda.empty_cache()
+    print(f"{label}: n = {n}, {nelec}, {ndet} determinants", flush=True)
+    print(f"  sigma {t_sigma * 1e3:.2f} ms", flush=True)
+    gemm = {}
+    for slabs in (None, 1):
+        rb = fci_gpu.RdmBuilder(be, n, nelec, chunk_rows=chunk_rows, slabs=slabs, held=8 * ndet)
+        whole = median_of_five(lambda: rb.rdm12(c))
+        phases = {"gather": [], "gemm": [], "finish": []}
+        for _ in range(5):
+            rb.seconds = {"gather": 0.0, "gemm": 0.0, "finish": 0.0}
+            rb.rdm12(c)
+            for k, v in rb.seconds.items():
+                phases[k].append(v)
+        rb.seconds = None
+        sec = {k: float(np.median(v)) for k, v in phases.items()}
+        gemm[rb.slabs] = sec["gemm"]
+        flops = 2 * g1 * g1 * ndet
+        print(f"  rdm12, {rb.slabs} slab(s), {rb.plan['chunks']} chunk(s): {whole * 1e3:.2f} ms = {whole / t_sigma:.2f} sigma "
+              f"(phases synchronised one by one: gather {sec['gather'] * 1e3:.2f} ms, GEMM {sec['gemm'] * 1e3:.2f} ms, "
+              f"{flops / sec['gemm'] / 1e12:.1f} TFLOP/s, finish {sec['finish'] * 1e3:.2f} ms)", flush=True)
+        if slabs is None:
+            t_rdm1 = median_of_five(lambda: rb.rdm1(c))
+            print(f"  direct rdm1 {t_rdm1 * 1e3:.2f} ms = {t_rdm1 / t_sigma:.2f} sigma", flush=True)
+        del rb
+        torch.cuda.empty_cache()
+    print("  GEMM by slabs: " + ", ".join(f"{k}: {v * 1e3:.2f} ms" for k, v in gemm.items()), flush=True)
+
+
 cfg = NbedConfig(geometry=WATER, n_active_atoms=1, basis="6-31g", xc_functional="hf", convergence=1e-10)
 hf = BuiltinHFProvider(be).global_hf(cfg)
 spatial = HamiltonianBuilder(hf, hf.energy_nuc(), backend=be).build_spatial_device()
@@ -83,6 +138,9 @@ if mo_occ.ndim == 1:
     mo_occ = np.array((mo_occ > 0, mo_occ > 1), dtype=float)
 occupied = [2 * int(i) for i in np.flatnonzero(mo_occ[0] > 0)] + [2 * int(i) + 1 for i in np.flatnonzero(mo_occ[1] > 0)]
 nelec = tuple(int(x) for x in hf.mol.nelec)
+if RDM:
+    time_rdm("water / 6-31G", spatial, nelec)
+    sys.exit(0)
 time_sigma("water / 6-31G", spatial, nelec)
 time_solve("water / 6-31G", spatial, nelec, occupied, 1e-8)
 
