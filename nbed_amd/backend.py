@@ -1324,21 +1324,25 @@ class HipBackend:
         self.axpby(1.0 / c, s, 0.0, y)  # y = S / c
         z = self.copy(eye)
         prev = None
-        done = False
+        last = -1
         for it in range(max_iter):
             t = self.copy(eye3)
             self.gemm(z, y, alpha=-1.0, beta=1.0, out=t)  # T' = 3 I - Z Y  (= 2 T)
-            if it % check_every == check_every - 1 or done:
+            if it % check_every == check_every - 1 or it == last:
                 r = self.copy(t)
                 self.axpby(-2.0, eye, 1.0, r)  # I - Z Y
                 res = float(np.sqrt(self.dots(r.reshape(-1), r.reshape(1, -1))[0]))
                 if not np.isfinite(res):
                     return None
-                if done or res < 1e-14 * n:
+                if it == last or res < 2.0 * np.finfo(np.float64).eps * n:  # (Z is off by res / 2)
                     break
-                # quadratic phase reached: one more step takes the residual to rounding level
-                if res < 1e-6 or (prev is not None and res > 0.5 * prev and res < 1e-9):
-                    done = True
+                # quadratic phase reached (a step takes the residual r to 3 r^2 / 4): one more step reaches
+                # rounding level from below 1e-8, two from below 1e-6
+                if last < 0:
+                    if res < 1e-8 or (prev is not None and res > 0.5 * prev and res < 1e-9):
+                        last = it + 1
+                    elif res < 1e-6:
+                        last = it + 2
                 prev = res
             y = self.gemm(y, t, alpha=0.5)
             z = self.gemm(t, z, alpha=0.5)

@@ -508,14 +508,15 @@ extern "C" int nbx_sym_pow_ns(nbx_ctx* ctx, int64_t n, const double* d_s, double
     NBX_LAUNCH_CHECK();
     int cur = 0;
     double prev = -1.0;
-    bool done = false, converged = false;
+    bool converged = false;
+    int last = -1;  // the step whose iterates are delivered, once the quadratic phase is reached
     int it = 0;
     for (; it < max_iter; ++it) {
         int rc = nbx_gemm(ctx, 'N', 'N', n, n, n, 1.0, z[cur], n, 0, y[cur], n, 0, 0.0, t, n, 0, 1);  // Z Y
         if (rc != NBX_OK) return rc;
         hipLaunchKernelGGL(ns_t_kernel, dim3((unsigned)tb), dim3(256), 0, ctx->stream, n, t, partial);  // T = 3 I - Z Y
         NBX_LAUNCH_CHECK();
-        if (it % check_every == check_every - 1 || done) {
+        if (it % check_every == check_every - 1 || it == last) {
             double hp[128];
             rc = nbx_memcpy_d2h(ctx, hp, partial, (size_t)tb * sizeof(double));
             if (rc != NBX_OK) return rc;
@@ -523,12 +524,19 @@ extern "C" int nbx_sym_pow_ns(nbx_ctx* ctx, int64_t n, const double* d_s, double
             for (int b = 0; b < tb; ++b) ss += hp[b];
             const double res = sqrt(ss);
             if (!(res == res) || res > 1.0e300) return NBX_OK;  // NaN / inf: not converged (*h_iters stays -1)
-            if (done || res < 1.0e-14 * (double)n) {
+            // Z is off by r / 2 at a residual r: below 2 N eps these iterates are at rounding level already (a well
+            // conditioned S sits at ~1e-15 here from its seventh step on)
+            if (it == last || res < 2.0 * 2.220446049250313e-16 * (double)n) {
                 converged = true;
                 break;
             }
-            // quadratic phase reached: one more step takes the residual to rounding level
-            if (res < 1.0e-6 || (prev >= 0.0 && res > 0.5 * prev && res < 1.0e-9)) done = true;
+            // quadratic phase reached: a step takes the residual r to 3 r^2 / 4, so one more step reaches rounding level
+            // from below 1e-8 and two from below 1e-6.  (Stopping one step after r < 1e-6 left 4e-13, and stopping AT
+            // r < 1e-14 N left 5e-13 at N = 181: 16 times and 2.4 times N eps cond(S) at cond 10.)
+            if (last < 0) {
+                if (res < 1.0e-8 || (prev >= 0.0 && res > 0.5 * prev && res < 1.0e-9)) last = it + 1;
+                else if (res < 1.0e-6) last = it + 2;
+            }
             prev = res;
         }
         rc = nbx_gemm(ctx, 'N', 'N', n, n, n, 0.5, y[cur], n, 0, t, n, 0, 0.0, y[cur ^ 1], n, 0, 1);  // Y T / 2
