@@ -1023,6 +1023,25 @@ int nbx_ccsd_tau(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_t1, c
  * device double d_maxerr.  d_t_new and d_err are typically a slot of the DIIS history.              */
 int nbx_ccsd_update(nbx_ctx* ctx, int64_t nocc, int64_t nvir, const double* d_r, const double* d_t_old,
                     const double* d_eo, const double* d_ev, double* d_t_new, double* d_err, double* d_maxerr);
+/* Lambda equations and density (csrc/ccsd_lambda.hip): what nbed_amd/ccsd_gpu.py needs besides GEMMs and permutes
+ * to give the CCSD of nbed/driver.py:1105-1135 its left-hand state and one-particle density.
+ *
+ * Disconnected term of the doubles Lambda equation, in one pass over d_r2 (nocc, nocc, nvir, nvir):
+ *      r2[i,j,a,b] += alpha ( x[i,a] y[j,b] - x[j,a] y[i,b] - x[i,b] y[j,a] + x[j,b] y[i,a] ),
+ * x and y (nocc, nvir), or (nvir, nocc) where the bit of `layout` is set (bit 0: x, bit 1: y).  Grid-stride, no
+ * atomics.  Does not synchronise.                                                                           */
+int nbx_ccsd_lambda_outer(nbx_ctx* ctx, int64_t nocc, int64_t nvir, double alpha, const double* d_x, const double* d_y,
+                          int layout, double* d_r2);
+/* Spin-resolved, symmetrised one-particle density d_dm1 (2, n, n), dm1[s,p,q] = <a+_{p s} a_{q s}>, in the original
+ * orbital order from its blocks over occupied / virtual spin orbitals: d_goo (nocc, nocc), d_gov (nocc, nvir), d_gvo
+ * (nvir, nocc), d_gvv (nvir, nvir), with d_occ and d_vir (device ints; together a permutation of [0, 2n), which the
+ * caller guarantees: every element of d_dm1 is then written once).  dm1 = 1/2 (gamma + gamma^T) + the occupations of
+ * the reference determinant.  The max |gamma[P,Q]| over pairs of different spins -- zero for a Hamiltonian of the
+ * spin-block form -- goes to the device double d_cross (NaN if any is).  One workgroup, no atomics.  Does not
+ * synchronise.                                                                                              */
+int nbx_ccsd_rdm1(nbx_ctx* ctx, int64_t n, int64_t nocc, int64_t nvir, const int* d_occ, const int* d_vir,
+                  const double* d_goo, const double* d_gov, const double* d_gvo, const double* d_gvv, double* d_dm1,
+                  double* d_cross);
 /* Perturbative triples (csrc/ccsd_t.hip): the (T) a PySCF user adds with ccsd_t() to the CCSD of
  * nbed/driver.py:1105-1135, in the non-HF form (f_ov != 0) over semicanonical spin orbitals (f_oo, f_vv
  * diagonal: d_eo, d_ev).  d_cubes holds ncubes <= 65535 cubes W (nvir, nvir, nvir), cube x that of the

@@ -236,6 +236,8 @@ SIGNATURES = {
     "nbx_pair_unpack": (c_int, [_P, c_int64, c_int64, c_int64, c_double, _P, c_double, _P]),
     "nbx_ccsd_tau": (c_int, [_P, c_int64, c_int64, _P, _P, c_double, c_double, c_double, c_int, _P]),
     "nbx_ccsd_update": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "nbx_ccsd_lambda_outer": (c_int, [_P, c_int64, c_int64, c_double, _P, _P, c_int, _P]),
+    "nbx_ccsd_rdm1": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nbx_ccsd_triples_worksize": (c_size_t, [c_int64, c_int64]),
     "nbx_ccsd_triples_tile": (c_int, []),
     "nbx_ccsd_triples_energy": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),

@@ -1760,6 +1760,37 @@ class HipBackend:
         self._call("nbx_ccsd_update", no, nv, self._p(r), self._p(t_old), self._p(eo), self._p(ev), self._p(t_new),
                    self._p(err), self._p(maxerr))
 
+    def ccsd_lambda_outer(self, x, y, r2, alpha: float = 1.0, x_transposed: bool = False, y_transposed: bool = False):
+        """r2[i,j,a,b] += alpha P(ij) P(ab) x[i,a] y[j,b] in place (csrc/ccsd_lambda.hip); an operand is (no, nv), or
+        (nv, no) with its ``*_transposed`` set."""
+        if r2.dim() != 4 or r2.shape[0] != r2.shape[1] or r2.shape[2] != r2.shape[3] or not r2.is_contiguous():
+            raise ValueError("ccsd_lambda_outer: r2 must be a contiguous (no, no, nv, nv) tensor")
+        no, nv = int(r2.shape[0]), int(r2.shape[2])
+        for t, tr in ((x, x_transposed), (y, y_transposed)):
+            if tuple(t.shape) != ((nv, no) if tr else (no, nv)) or not t.is_contiguous() or t.dtype != r2.dtype:
+                raise ValueError("ccsd_lambda_outer: operand shapes")
+        self._call("nbx_ccsd_lambda_outer", no, nv, float(alpha), self._p(x), self._p(y),
+                   int(bool(x_transposed)) | (int(bool(y_transposed)) << 1), self._p(r2))
+        return r2
+
+    def ccsd_rdm1(self, occ, vir, goo, gov, gvo, gvv):
+        """(dm1 (2, n, n) device tensor, max |cross-spin element| device double) from the density blocks over the
+        occupied / virtual spin orbitals ``occ`` / ``vir`` (host index lists, together a permutation of [0, 2n)):
+        symmetrised, reference occupations added, original orbital order (csrc/ccsd_lambda.hip)."""
+        occ, vir = [int(i) for i in occ], [int(i) for i in vir]
+        no, nv = len(occ), len(vir)
+        nso = no + nv
+        if nso % 2 or nso == 0 or sorted(occ + vir) != list(range(nso)):
+            raise ValueError("ccsd_rdm1: occ and vir must together be a permutation of the 2n spin-orbital indices")
+        for t, shape in ((goo, (no, no)), (gov, (no, nv)), (gvo, (nv, no)), (gvv, (nv, nv))):
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("ccsd_rdm1: block shapes")
+        n = nso // 2
+        dm1, cross = self.empty((2, n, n)), self.empty(1)
+        d_occ, d_vir = self.index_array(occ, nso), self.index_array(vir, nso)
+        self._call("nbx_ccsd_rdm1", n, no, nv, self._p(d_occ), self._p(d_vir), self._p(goo), self._p(gov), self._p(gvo), self._p(gvv), self._p(dm1), self._p(cross))
+        return dm1, cross
+
     def read_scalars(self, d) -> np.ndarray:
         """A few device doubles -> host (synchronises)."""
         out = (c_double * d.numel())()
@@ -1791,7 +1822,7 @@ class HipBackend:
 
     def ccsd(self, spatial, occupied, **kwargs):
         """Spin-orbital CCSD on the device (``nbed_amd.ccsd_gpu.solve_spatial``): the capability the driver asks for;
-        ``triples=True`` adds the (T) energy as ``e_t``."""
+        ``triples=True`` adds the (T) energy as ``e_t``, ``density=True`` the Lambda amplitudes and ``rdm1()``."""
         from . import ccsd_gpu
 
         return ccsd_gpu.solve_spatial(spatial, occupied, backend=self, **kwargs)

@@ -25,7 +25,8 @@ class CCSDResult:
     """Duck-typed stand-in for ``pyscf.cc.CCSD``: ``e_tot``, ``e_corr``, ``e_hf``, ``converged``, ``t1``, ``t2``; with
     the perturbative triples asked for, ``e_t`` and ``e_tot_t`` = ``e_tot + e_t`` (both ``None`` otherwise)."""
 
-    def __init__(self, e_hf, e_corr, t1, t2, converged, iterations, e_t=None):
+    def __init__(self, e_hf, e_corr, t1, t2, converged, iterations, e_t=None, l1=None, l2=None, lambda_converged=None,
+                 lambda_iterations=None, dm1=None):
         self.e_hf = float(e_hf)
         self.e_corr = float(e_corr)
         self.e_tot = float(e_hf + e_corr)
@@ -34,6 +35,26 @@ class CCSDResult:
         self.iterations = int(iterations)
         self.e_t = None if e_t is None else float(e_t)
         self.e_tot_t = None if e_t is None else self.e_tot + self.e_t
+        # the left-hand state and its density (``solve(..., density=True)``; None otherwise)
+        self.l1, self.l2 = l1, l2
+        self.lambda_converged = None if lambda_converged is None else bool(lambda_converged)
+        self.lambda_iterations = None if lambda_iterations is None else int(lambda_iterations)
+        self._dm1 = dm1
+
+    def rdm1(self) -> np.ndarray:
+        """(2, n, n): dm1[s, p, q] = <a+_{p s} a_{q s}> of CCSD, the convention of ``FCIResult.rdm1`` (spin orbital
+        2p + s, alpha even): the symmetric part of the orbital-unrelaxed response density
+        <0|(1 + Lambda) e^{-T} a+_p a_q e^{T}|0>, the occupations of the reference determinant included.  With
+        ``triples`` it still is the CCSD density: (T) has none here."""
+        if self._dm1 is None:
+            raise ValueError("this CCSD result has no density: solve(..., density=True) solves the Lambda equations "
+                             "and builds it")
+        return self._dm1.copy()
+
+    def natural_occupations(self) -> np.ndarray:
+        """Eigenvalues of the spin-summed ``rdm1``, descending (as ``FCIResult.natural_occupations``)."""
+        dm = self.rdm1()
+        return np.linalg.eigvalsh(dm[0] + dm[1])[::-1].copy()
 
 
 def antisymmetrized(h2: np.ndarray) -> np.ndarray:
@@ -44,9 +65,10 @@ def antisymmetrized(h2: np.ndarray) -> np.ndarray:
 
 
 def solve(constant: float, h1: np.ndarray, h2: np.ndarray, occupied, conv_tol: float = 1e-10, max_cycle: int = 200,
-          diis_space: int = 6, triples: bool = False) -> CCSDResult:
+          diis_space: int = 6, triples: bool = False, density: bool = False) -> CCSDResult:
     """CCSD amplitudes and energy for the determinant that occupies the spin orbitals ``occupied``; ``triples``: also
-    the (T) energy of ``triples_correction`` from the final amplitudes."""
+    the (T) energy of ``triples_correction`` from the final amplitudes; ``density``: also the Lambda amplitudes
+    (``solve_lambda``) and the one-particle density of ``CCSDResult.rdm1`` -- CCSD's, with or without ``triples``."""
     nso = h1.shape[0]
     if nso > MAX_SPIN_ORBITALS:
         raise ValueError(f"nbed_amd.ccsd is limited to {MAX_SPIN_ORBITALS} spin orbitals (got {nso})")
@@ -146,7 +168,183 @@ def solve(constant: float, h1: np.ndarray, h2: np.ndarray, occupied, conv_tol: f
             break
         e_old = e_new
     e_t = triples_correction(h1, h2, occ, t1, t2) if triples else None
-    return CCSDResult(e_hf, e_old, t1, t2, converged, it, e_t)
+    extra = {}
+    if density:
+        blocks = dict(oovv=oovv, oooo=oooo, vvvv=vvvv, ovvo=ovvo, ooov=ooov, ovvv=ovvv, vvvo=vvvo)
+        l1, l2, l_conv, l_it = solve_lambda(t1, t2, fov, foo_od, fvv_od, d1, d2, blocks, conv_tol, max_cycle, diis_space)
+        dm1, _ = spin_resolved_density(density_blocks(t1, t2, l1, l2), occ, vir, nso)
+        extra = dict(l1=l1, l2=l2, lambda_converged=l_conv, lambda_iterations=l_it, dm1=dm1)
+    return CCSDResult(e_hf, e_old, t1, t2, converged, it, e_t, **extra)
+
+
+# ---------------------------------------------------------------------------------------------------- Lambda
+CROSS_SPIN_TOL = 1e-10
+
+
+def _p_ij(x):
+    return x - x.transpose(1, 0, 2, 3)
+
+
+def _p_ab(x):
+    return x - x.transpose(0, 1, 3, 2)
+
+
+def lambda_intermediates(t1, t2, fov, foo_od, fvv_od, blocks) -> dict:
+    """The elements of e^{-T} H e^{T} the Lambda equations read (Gauss, Stanton, J. Chem. Phys. 103, 3561 (1995),
+    spin-orbital form, general Fock matrix), none of which depends on Lambda: they are built once.  ``foo_od`` and
+    ``fvv_od`` are f_oo and f_vv without their diagonals, which the denominators carry.  W_abef is not among them, and
+    W_abei comes without its t_if W_abef term: both are folded into the ladder of ``lambda_residual``.
+
+        F_me   = f_me + t_nf <mn||ef>
+        F_ae   = f_ae - 1/2 f_me t_ma + t_mf <ma||fe> - 1/2 tau~_mnaf <mn||ef> - 1/2 t_ma F_me
+        F_mi   = f_mi + 1/2 t_ie f_me + t_ne <mn||ie> + 1/2 tau~_inef <mn||ef> + 1/2 t_ie F_me
+        W_mnij = <mn||ij> + P(ij) t_je <mn||ie> + 1/2 tau_ijef <mn||ef>
+        W_mbej = <mb||ej> + t_jf <mb||ef> + t_nb <mn||je> - (t_jnfb + t_jf t_nb) <mn||ef>
+        W_mnie = <mn||ie> + t_if <mn||fe>
+        W_maef = <ma||ef> - t_na <mn||ef>                                          (= -W_amef)
+        W_mbij = <ij||mb> - F_me t_ijbe - t_nb W_mnij + 1/2 <mb||ef> tau_ijef
+                 + P(ij) [ <mn||ie> t_jnbe + t_ie (<mb||ej> - t_njbf <mn||ef>) ]
+        W_abei = <ab||ei> - F_me t_miab - 1/2 <mn||ie> tau_mnab
+                 - P(ab) [ <mb||ef> t_miaf + t_ma (<mb||ei> - t_nibf <mn||ef>) ]      (+ t_if W_abef: see above)
+    """
+    oovv, oooo, ovvo, ooov, ovvv, vvvo = (blocks[k] for k in ("oovv", "oooo", "ovvo", "ooov", "ovvv", "vvvo"))
+    pair = np.einsum("ia,jb->ijab", t1, t1)
+    tau = t2 + pair - pair.transpose(0, 1, 3, 2)
+    tau_t = t2 + 0.5 * (pair - pair.transpose(0, 1, 3, 2))
+    fme = fov + np.einsum("nf,mnef->me", t1, oovv)
+    fae = fvv_od - 0.5 * np.einsum("me,ma->ae", fov, t1) + np.einsum("mf,mafe->ae", t1, ovvv) \
+        - 0.5 * np.einsum("mnaf,mnef->ae", tau_t, oovv) - 0.5 * np.einsum("ma,me->ae", t1, fme)
+    fmi = foo_od + 0.5 * np.einsum("ie,me->mi", t1, fov) + np.einsum("ne,mnie->mi", t1, ooov) \
+        + 0.5 * np.einsum("inef,mnef->mi", tau_t, oovv) + 0.5 * np.einsum("ie,me->mi", t1, fme)
+    wmnij = oooo + np.einsum("je,mnie->mnij", t1, ooov) - np.einsum("ie,mnje->mnij", t1, ooov) \
+        + 0.5 * np.einsum("ijef,mnef->mnij", tau, oovv)
+    wmbej = ovvo + np.einsum("jf,mbef->mbej", t1, ovvv) + np.einsum("nb,mnje->mbej", t1, ooov) \
+        - np.einsum("jnfb,mnef->mbej", t2 + pair, oovv)
+    wmnie = ooov + np.einsum("if,mnfe->mnie", t1, oovv)
+    wmaef = ovvv - np.einsum("na,mnef->maef", t1, oovv)
+    ring = ovvo - np.einsum("njbf,mnef->mbej", t2, oovv)
+    wmbij = ooov.transpose(2, 3, 0, 1) - np.einsum("me,ijbe->mbij", fme, t2) - np.einsum("nb,mnij->mbij", t1, wmnij) \
+        + 0.5 * np.einsum("mbef,ijef->mbij", ovvv, tau)
+    tmp = np.einsum("mnie,jnbe->mbij", ooov, t2) + np.einsum("ie,mbej->mbij", t1, ring)
+    wmbij += tmp - tmp.transpose(0, 1, 3, 2)
+    wabei = vvvo - np.einsum("me,miab->abei", fme, t2) - 0.5 * np.einsum("mnie,mnab->abei", ooov, tau)
+    tmp = np.einsum("mbef,miaf->abei", ovvv, t2) + np.einsum("ma,mbei->abei", t1, ring)
+    wabei -= tmp - tmp.transpose(1, 0, 2, 3)
+    return dict(tau=tau, fme=fme, fae=fae, fmi=fmi, wmnij=wmnij, wmbej=wmbej, wmnie=wmnie, wmaef=wmaef, wmbij=wmbij,
+                wabei=wabei)
+
+
+def lambda_residual(l1, l2, t1, t2, blocks, im):
+    """Right-hand sides (r1, r2) of the Lambda equations, lambda_new = r / D:
+
+        r1_ia   = F_ia + l_ie F_ea - l_ma F_im + l_me W_ieam + 1/2 l_imef W_efam + L_imae t_me - 1/2 l_mnae W_iemn
+                  + G_ef W_iefa - G_mn W_mina
+        r2_ijab = <ij||ab> + P(ab) l_ijae F_eb - P(ij) l_imab F_jm + 1/2 l_mnab W_ijmn + L_ijab - P(ij) l_ie W_jeab
+                  - P(ab) l_ma W_ijmb + P(ij) P(ab) [ l_imae W_jebm + l_ia F_jb ] + P(ab) <ij||ae> G_be
+                  - P(ij) <im||ab> G_mj
+        G_ae    = -1/2 t_mnef l_mnaf,    G_mi = 1/2 t_mnef l_inef
+        L_ijab  = 1/2 l_ijef W_efab = 1/2 l_ijef <ef||ab> + (l_ijef t_mf) <me||ab> + 1/4 (l_ijef tau_mnef) <mn||ab>
+
+    with the W of ``lambda_intermediates`` (W_iefa = W_maef there).  L is the particle-particle ladder: its first
+    piece is the only O(o^2 v^4) product, the other two go through an o^3 v and an o^4 intermediate, and L t1 is the
+    t_if W_abef term of W_abei in r1."""
+    oovv, vvvv, ovvv = blocks["oovv"], blocks["vvvv"], blocks["ovvv"]
+    fme, fae, fmi = im["fme"], im["fae"], im["fmi"]
+    gae = -0.5 * np.einsum("mnef,mnaf->ae", t2, l2)
+    gmi = 0.5 * np.einsum("mnef,inef->mi", t2, l2)
+    lad = 0.5 * np.einsum("ijef,efab->ijab", l2, vvvv)
+    lad += np.einsum("ijem,meab->ijab", np.einsum("ijef,mf->ijem", l2, t1), ovvv)
+    lad += 0.25 * np.einsum("ijmn,mnab->ijab", np.einsum("ijef,mnef->ijmn", l2, im["tau"]), oovv)
+    r1 = fme + np.einsum("ie,ea->ia", l1, fae) - np.einsum("ma,im->ia", l1, fmi) \
+        + np.einsum("me,ieam->ia", l1, im["wmbej"]) + 0.5 * np.einsum("imef,efam->ia", l2, im["wabei"]) \
+        + np.einsum("imae,me->ia", lad, t1) - 0.5 * np.einsum("mnae,iemn->ia", l2, im["wmbij"]) \
+        + np.einsum("ef,iefa->ia", gae, im["wmaef"]) - np.einsum("mn,mina->ia", gmi, im["wmnie"])
+    r2 = oovv + 0.5 * np.einsum("mnab,ijmn->ijab", l2, im["wmnij"]) + lad
+    r2 += _p_ab(np.einsum("ijae,eb->ijab", l2, fae) + np.einsum("ijae,be->ijab", oovv, gae)
+                - np.einsum("ma,ijmb->ijab", l1, im["wmnie"]))
+    r2 -= _p_ij(np.einsum("imab,jm->ijab", l2, fmi) + np.einsum("imab,mj->ijab", oovv, gmi)
+                + np.einsum("ie,jeab->ijab", l1, im["wmaef"]))
+    r2 += _p_ij(_p_ab(np.einsum("imae,jebm->ijab", l2, im["wmbej"]) + np.einsum("ia,jb->ijab", l1, fme)))
+    return r1, r2
+
+
+def solve_lambda(t1, t2, fov, foo_od, fvv_od, d1, d2, blocks, conv_tol=1e-10, max_cycle=200, diis_space=6):
+    """(l1, l2, converged, cycles): the CCSD Lambda amplitudes, l1 (o, v) and l2 (o, o, v, v) laid out like t1 and t2,
+    by the amplitude loop's iteration -- lambda_new = r / D, DIIS of ``diis_space`` from the second stored vector --
+    from the first-order left state l1 = t1, l2 = t2, until max |lambda_new - lambda| < 10 max(conv_tol, 1e-9)."""
+    im = lambda_intermediates(t1, t2, fov, foo_od, fvv_od, blocks)
+    l1, l2 = t1.copy(), t2.copy()
+    no, nv = t1.shape
+    hist_l, hist_e = [], []
+    converged, it = False, 0
+    for it in range(1, max_cycle + 1):
+        r1, r2 = lambda_residual(l1, l2, t1, t2, blocks, im)
+        vec = np.concatenate([(r1 / d1).ravel(), (r2 / d2).ravel()])
+        err = vec - np.concatenate([l1.ravel(), l2.ravel()])
+        hist_l.append(vec)
+        hist_e.append(err)
+        hist_l, hist_e = hist_l[-diis_space:], hist_e[-diis_space:]
+        if len(hist_l) > 1:
+            m = len(hist_l)
+            b = -np.ones((m + 1, m + 1))
+            b[m, m] = 0.0
+            for i in range(m):
+                for j in range(m):
+                    b[i, j] = hist_e[i] @ hist_e[j]
+            rhs = np.zeros(m + 1)
+            rhs[m] = -1.0
+            try:
+                c = np.linalg.solve(b, rhs)[:m]
+                vec = sum(ci * li for ci, li in zip(c, hist_l))
+            except np.linalg.LinAlgError:
+                pass
+        l1, l2 = vec[: no * nv].reshape(no, nv), vec[no * nv:].reshape(no, no, nv, nv)
+        if np.abs(err).max() < max(conv_tol, 1e-9) * 10:
+            converged = True
+            break
+    return l1, l2, converged, it
+
+
+def density_blocks(t1, t2, l1, l2) -> dict:
+    """The four blocks of the unrelaxed CCSD response density gamma[p, q] = <0|(1 + Lambda) e^{-T} {a+_p a_q} e^{T}|0>
+    over (occupied | virtual) spin orbitals, the reference occupations not included:
+
+        oo[i,j] = -l_ie t_je - 1/2 l_imef t_jmef            vv[a,b] = l_ma t_mb + 1/2 l_mnae t_mnbe
+        ov[i,a] = l_ia
+        vo[a,i] = t_ia + l_me t_imae - X_mi t_ma - t_ie Y_ae,   X_mi = 1/2 l_mnef t_inef,
+                                                                Y_ae = 1/2 l_mnef t_mnaf + l_me t_ma
+    """
+    x = 0.5 * np.einsum("mnef,inef->mi", l2, t2)
+    y = 0.5 * np.einsum("mnef,mnaf->ae", l2, t2) + np.einsum("me,ma->ae", l1, t1)
+    return {
+        "oo": -np.einsum("ie,je->ij", l1, t1) - 0.5 * np.einsum("imef,jmef->ij", l2, t2),
+        "vv": np.einsum("ma,mb->ab", l1, t1) + 0.5 * np.einsum("mnae,mnbe->ab", l2, t2),
+        "ov": l1.copy(),
+        "vo": t1.T + np.einsum("imae,me->ai", t2, l1) - np.einsum("mi,ma->ai", x, t1) - np.einsum("ie,ae->ai", t1, y),
+    }
+
+
+def spin_resolved_density(blocks: dict, occ, vir, nso: int):
+    """(dm1 (2, n, n), max |cross-spin element|) from the blocks of ``density_blocks`` and the spin orbitals they are
+    over: the blocks are scattered to the original spin-orbital order, the reference occupations added, the matrix
+    symmetrised, and its alpha-alpha and beta-beta parts returned.  The alpha-beta elements vanish for a Hamiltonian of
+    the form ``build()`` produces; past ``CROSS_SPIN_TOL`` they are an error, never dropped silently."""
+    occ, vir = np.asarray(occ, dtype=int), np.asarray(vir, dtype=int)
+    g = np.zeros((nso, nso))
+    g[np.ix_(occ, occ)] = blocks["oo"] + np.eye(len(occ))
+    g[np.ix_(occ, vir)] = blocks["ov"]
+    g[np.ix_(vir, occ)] = blocks["vo"]
+    g[np.ix_(vir, vir)] = blocks["vv"]
+    cross = float(max(np.abs(g[0::2, 1::2]).max(initial=0.0), np.abs(g[1::2, 0::2]).max(initial=0.0)))
+    check_cross_spin(cross)
+    g = 0.5 * (g + g.T)
+    return np.stack([g[0::2, 0::2], g[1::2, 1::2]]), cross
+
+
+def check_cross_spin(cross: float) -> None:
+    if not cross <= CROSS_SPIN_TOL:
+        raise ValueError(f"the CCSD density couples alpha and beta spin orbitals (max |element| {cross:.3e} > "
+                         f"{CROSS_SPIN_TOL:g}): the Hamiltonian is not of the spin-block form build() produces")
 
 
 # ---------------------------------------------------------------------------------------------------- (T)

@@ -15,7 +15,11 @@ dense numpy einsum on the host, for up to 40 spin orbitals.  This module is that
   ``ccsd.solve``, so the iterates follow the host solver's and can be compared cycle by cycle;
 * ``triples=True``: after the loop the (T) energy of ``ccsd.triples_correction`` from the device-resident amplitudes and
   blocks (``triples_from_blocks``): semicanonical rotation, one v x v^2 cube per occupied triple from six ``nbx_gemm``
-  calls, antisymmetriser, denominators and energy sum in ``nbx_ccsd_triples_energy`` (csrc/ccsd_t.hip).
+  calls, antisymmetriser, denominators and energy sum in ``nbx_ccsd_triples_energy`` (csrc/ccsd_t.hip);
+* ``density=True``: after the loop the Lambda equations of ``ccsd.solve_lambda`` on the same device-resident blocks and
+  amplitudes (``lambda_from_blocks``: the same ``Contractor``, the same packed ladder against ``vvvv_p``, the same
+  update kernel and DIIS, in the amplitude loop's own history buffers) and the one-particle density of
+  ``CCSDResult.rdm1`` (``nbx_ccsd_lambda_outer``, ``nbx_ccsd_rdm1``: csrc/ccsd_lambda.hip).
 
 ``torch`` only allocates and views; per cycle three groups of scalars reach the host (energy, max |err|, DIIS dots).
 """
@@ -48,7 +52,7 @@ def block_sizes(no: int, nv: int) -> dict:
     return sizes
 
 
-def memory_plan(no: int, nv: int, diis_space: int = 6) -> dict:
+def memory_plan(no: int, nv: int, diis_space: int = 6, density: bool = False) -> dict:
     """Bytes the device solver needs, by group, computed before anything is allocated (host arithmetic):
 
     blocks     the nine Hamiltonian blocks of ``block_sizes``
@@ -58,6 +62,10 @@ def memory_plan(no: int, nv: int, diis_space: int = 6) -> dict:
     work       the largest set of intermediates and permute buffers alive at once: W_mbej, the 1/2 t2 + t1 t1 of
                its last term, three o^2 v^2 temporaries, two <ov||vv>-sized permute buffers, the packed ladder
                result and its half-unpacked form
+    lambda     only with ``density``: what the Lambda loop holds beyond the above -- it reuses the residual, the DIIS
+               history and, for its per-cycle temporaries, the work space of the amplitude loop: [l1 | l2], the
+               packed l2, W_abei and W_maef with one more <ov||vv>-sized buffer while they are built, W_mbij and
+               W_mnie, W_mbej and the ladder L, W_mnij
     """
     n = (no + nv + 1) // 2
     nvec = no * nv + (no * nv) ** 2
@@ -69,6 +77,8 @@ def memory_plan(no: int, nv: int, diis_space: int = 6) -> dict:
         "amplitudes": 8 * (2 * nvec + 2 * diis_space * nvec + 2 * o2v2 + _npair(no) * _npair(nv)),
         "work": 8 * (5 * o2v2 + 2 * ovvv + _npair(no) * _npair(nv) + _npair(no) * nv * nv + no**3 * nv + no**4),
     }
+    if density:
+        plan["lambda"] = 8 * (nvec + _npair(no) * _npair(nv) + 3 * ovvv + 2 * no**3 * nv + 2 * o2v2 + no**4)
     plan["total"] = sum(plan.values())
     return plan
 
@@ -207,12 +217,13 @@ def spatial_from_dense(h1: np.ndarray, h2: np.ndarray):
 
 
 def solve(constant, h1, h2, occupied, conv_tol: float = 1e-10, max_cycle: int = 200, diis_space: int = 6,
-          backend=None, triples: bool = False, triples_batch: int | None = None) -> CCSDResult:
+          backend=None, triples: bool = False, triples_batch: int | None = None, density: bool = False,
+          stats: dict | None = None) -> CCSDResult:
     """``ccsd.solve`` on the device, from the dense spin-orbital tensors of ``build()`` (direct use and tests; the driver
     calls ``solve_spatial``, which never holds a (2n)^4 tensor)."""
     one, two = spatial_from_dense(h1, h2)
     return solve_spatial((constant, one, two), occupied, conv_tol=conv_tol, max_cycle=max_cycle, diis_space=diis_space,
-                         backend=backend, triples=triples, triples_batch=triples_batch)
+                         backend=backend, triples=triples, triples_batch=triples_batch, density=density, stats=stats)
 
 
 def _device_backend(backend):
@@ -323,14 +334,18 @@ def triples_from_blocks(t1, t2, fov, foo, fvv, oovv, ovvv, ovoo, occ_spins, vir_
 
 
 def solve_spatial(spatial, occupied, conv_tol: float = 1e-10, max_cycle: int = 200, diis_space: int = 6, backend=None,
-                  stats: dict | None = None, triples: bool = False, triples_batch: int | None = None) -> CCSDResult:
+                  stats: dict | None = None, triples: bool = False, triples_batch: int | None = None,
+                  density: bool = False) -> CCSDResult:
     """CCSD of the determinant that occupies the spin orbitals ``occupied`` (index 2p + s, alpha even).
 
     ``spatial``: a ``SpatialHamiltonian``, or ``(constant, one_body (2,n,n), two_body (3,n,n,n,n))`` with the blocks of
     ``build_spatial()`` (thresholded, the two-body ones halved) as host or device arrays.  ``stats``, if given, receives
     the bytes planned and the seconds per cycle.  ``triples``: after the loop, the (T) energy of
     ``triples_from_blocks`` from the device-resident amplitudes and blocks, as ``e_t`` of the result; ``triples_batch``:
-    its cubes in flight (default: what ``default_triples_batch`` fits into the free memory)."""
+    its cubes in flight (default: what ``default_triples_batch`` fits into the free memory).  ``density``: after the
+    loop (and before (T) frees what it does not read) the Lambda equations of ``lambda_from_blocks`` and the
+    one-particle density: ``l1``, ``l2``, ``lambda_converged`` and ``rdm1()`` of the result.  With ``triples`` as well
+    the density still is CCSD's: (T) contributes to the energy only."""
     be = _device_backend(backend)
     if hasattr(spatial, "two_body"):
         constant, one, two = spatial.constant, spatial.one_body, spatial.two_body
@@ -347,14 +362,16 @@ def solve_spatial(spatial, occupied, conv_tol: float = 1e-10, max_cycle: int = 2
         raise ValueError("CCSD needs at least one occupied and one virtual spin orbital")
     if not 1 <= diis_space <= 16:
         raise ValueError("diis_space must be between 1 and 16")
-    plan = memory_plan(no, nv, diis_space)
+    plan = memory_plan(no, nv, diis_space, density=density)
     held = 8 * 3 * n**4 if be.torch.is_tensor(two) and two.is_cuda else 0  # (device blocks are there already)
     free = be.free_bytes()
     if plan["total"] - held > free:
         raise NbedDriverError(
             f"device CCSD of {nso} spin orbitals ({no} occupied, {nv} virtual) needs {plan['total'] - held} bytes of "
             f"device memory ({plan['blocks']} for the Hamiltonian blocks, {plan['amplitudes']} for amplitudes and DIIS "
-            f"history, {plan['work']} of work space); {free} are free")
+            f"history, {plan['work']} of work space"
+            + (f", {plan['lambda']} for the Lambda amplitudes and their intermediates" if density else "")
+            + f"); {free} are free")
     if stats is not None:
         stats.update(plan=plan, nso=nso, nocc=no, nvir=nv)
 
@@ -514,6 +531,11 @@ def solve_spatial(spatial, occupied, conv_tol: float = 1e-10, max_cycle: int = 2
     if stats is not None:
         stats.update(cycle_seconds=cycle_seconds, iterations=it)
     t1_h, t2_h = be.to_host(t1).copy(), be.to_host(t2).copy()
+    extra = {}
+    if density:
+        # the amplitude loop's residual and DIIS history are dead: the Lambda loop runs in them
+        extra = lambda_from_blocks(be, occ, vir, amp, fov, foo_od, fvv_od, eo, ev, g, vvvv_p, tau, res, hist_t, hist_e,
+                                   conv_tol=conv_tol, max_cycle=max_cycle, stats=stats)
     e_t = None
     if triples:
         # (T) from what is on the device now, after the loop's own memory is handed back: the DIIS history, the packed
@@ -522,4 +544,195 @@ def solve_spatial(spatial, occupied, conv_tol: float = 1e-10, max_cycle: int = 2
         be.torch.cuda.empty_cache()
         e_t = triples_from_blocks(t1, t2, fov, foo_h, fvv_h, oovv, ovvv, ovoo, [p & 1 for p in occ], [p & 1 for p in vir],
                                   batch=triples_batch, backend=be, stats=stats)
-    return CCSDResult(e_hf, e_old, t1_h, t2_h, converged, it, e_t)
+    return CCSDResult(e_hf, e_old, t1_h, t2_h, converged, it, e_t, **extra)
+
+
+def lambda_from_blocks(be, occ, vir, amp, fov, foo_od, fvv_od, eo, ev, g, vvvv_p, tau, res, hist_l, hist_e,
+                       conv_tol: float = 1e-10, max_cycle: int = 200, stats: dict | None = None) -> dict:
+    """The CCSD Lambda amplitudes and the one-particle density on the device, from what the amplitude loop of
+    ``solve_spatial`` leaves there: the converged ``amp`` = [t1 | t2], the Fock blocks (``foo_od``, ``fvv_od``: without
+    their diagonals ``eo``, ``ev``), the Hamiltonian blocks ``g`` and the packed <vv||vv>, tau, and three buffers that
+    are dead by now and are overwritten: the residual ``res`` and the DIIS history ``hist_l``, ``hist_e``.
+
+    The equations are those of ``ccsd.lambda_intermediates`` / ``ccsd.lambda_residual``, term by term in their order,
+    every product through ``Contractor``.  The intermediates do not depend on Lambda and are built once.  W_abef is
+    never formed: 1/2 l_ijef <ef||ab> runs over packed pairs against ``vvvv_p`` (l2 packed by ``pair_pack``), the
+    t1 <ov||vv> pieces of the ladder go through Y_ijem = l_ijef t_mf (o^3 v), the 1/4 tau <oo||vv> piece through
+    l_ijef tau_mnef (o^4), and the t_if W_abef term of W_abei is the finished ladder times t1.  Start, update
+    (``nbx_ccsd_update``: same vector layout, same denominators), DIIS and stopping rule are ``ccsd.solve_lambda``'s.
+
+    Returns the keyword arguments ``CCSDResult`` takes: ``l1``, ``l2``, ``lambda_converged``, ``lambda_iterations``,
+    ``dm1``."""
+    from . import ccsd as host
+
+    c = Contractor(be)
+    no, nv = len(occ), len(vir)
+    n1, nvec = no * nv, no * nv + (no * nv) ** 2
+    diis_space = int(hist_l.shape[0])
+    oovv, oooo, ovvo, ooov, ovvv, vvvo, ovoo = (g[k] for k in ("oovv", "oooo", "ovvo", "ooov", "ovvv", "vvvo", "ovoo"))
+    t1, t2 = amp[:n1].view(no, nv), amp[n1:].view(no, no, nv, nv)
+    r1, r2 = res[:n1].view(no, nv), res[n1:].view(no, no, nv, nv)
+    ident, swap_ab, swap_ij, swap_both = [0, 1, 2, 3], [0, 1, 3, 2], [1, 0, 2, 3], [1, 0, 3, 2]
+    t_setup = time.perf_counter()
+    # ---- the elements of e^-T H e^T (ccsd.lambda_intermediates)
+    tau_t = be.ccsd_tau(t1, t2, 1.0, 0.5, 0.5)
+    fme = be.copy(fov)
+    c("nf,mnef->me", t1, oovv, 1.0, fme, 1.0)
+    fae = be.copy(fvv_od)
+    c("me,ma->ae", fov, t1, -0.5, fae, 1.0)
+    c("mf,mafe->ae", t1, ovvv, 1.0, fae, 1.0)
+    c("mnaf,mnef->ae", tau_t, oovv, -0.5, fae, 1.0)
+    c("ma,me->ae", t1, fme, -0.5, fae, 1.0)
+    fmi = be.copy(foo_od)
+    c("ie,me->mi", t1, fov, 0.5, fmi, 1.0)
+    c("ne,mnie->mi", t1, ooov, 1.0, fmi, 1.0)
+    c("inef,mnef->mi", tau_t, oovv, 0.5, fmi, 1.0)
+    c("ie,me->mi", t1, fme, 0.5, fmi, 1.0)
+    del tau_t
+    wmnij = be.copy(oooo)
+    c("je,mnie->mnij", t1, ooov, 1.0, wmnij, 1.0)
+    c("ie,mnje->mnij", t1, ooov, -1.0, wmnij, 1.0)
+    c("ijef,mnef->mnij", tau, oovv, 0.5, wmnij, 1.0)
+    wmbej = be.copy(ovvo)
+    c("jf,mbef->mbej", t1, ovvv, 1.0, wmbej, 1.0)
+    c("nb,mnje->mbej", t1, ooov, 1.0, wmbej, 1.0)
+    full = be.ccsd_tau(t1, t2, 1.0, 1.0, 0.0)  # t2_jnfb + t1_jf t1_nb
+    c("jnfb,mnef->mbej", full, oovv, -1.0, wmbej, 1.0)
+    del full
+    wmnie = be.copy(ooov)
+    c("if,mnfe->mnie", t1, oovv, 1.0, wmnie, 1.0)
+    wmaef = be.copy(ovvv)
+    c("na,mnef->maef", t1, oovv, -1.0, wmaef, 1.0)
+    ring = be.copy(ovvo)  # <mb||ej> - t_njbf <mn||ef>
+    c("njbf,mnef->mbej", t2, oovv, -1.0, ring, 1.0)
+    wmbij = be.copy(ovoo)  # <mb||ij> = <ij||mb>
+    c("me,ijbe->mbij", fme, t2, -1.0, wmbij, 1.0)
+    c("nb,mnij->mbij", t1, wmnij, -1.0, wmbij, 1.0)
+    c("mbef,ijef->mbij", ovvv, tau, 0.5, wmbij, 1.0)
+    tmp = c("mnie,jnbe->mbij", ooov, t2)
+    c("ie,mbej->mbij", t1, ring, 1.0, tmp, 1.0)
+    be.permute4(tmp, ident, 1.0, 1.0, wmbij)
+    be.permute4(tmp, swap_ab, -1.0, 1.0, wmbij)  # (the last two axes: i <-> j)
+    wabei = be.copy(vvvo)
+    c("me,miab->abei", fme, t2, -1.0, wabei, 1.0)
+    c("mnie,mnab->abei", ooov, tau, -0.5, wabei, 1.0)
+    tmp = c("mbef,miaf->abei", ovvv, t2)
+    c("ma,mbei->abei", t1, ring, 1.0, tmp, 1.0)
+    be.permute4(tmp, ident, -1.0, 1.0, wabei)
+    be.permute4(tmp, swap_ij, 1.0, 1.0, wabei)  # (the first two axes: a <-> b)
+    del tmp, ring
+    be.read_scalars(fme.view(-1)[:1])  # (synchronises: the seconds below are the intermediates', not their launches')
+    setup_seconds = time.perf_counter() - t_setup
+
+    # ---- the loop (ccsd.solve_lambda): first-order left state, lambda_new = r / D, DIIS
+    lam = be.empty(nvec)
+    lam.copy_(amp)
+    l1, l2 = lam[:n1].view(no, nv), lam[n1:].view(no, no, nv, nv)
+    maxerr = be.empty(1)
+    npo, npv = _npair(no), _npair(nv)
+    lad = be.empty((no, no, nv, nv))
+    bmat = np.zeros((diis_space, diis_space))
+    age = []
+    converged, it = False, 0
+    cycle_seconds = []
+    for it in range(1, max_cycle + 1):
+        t_start = time.perf_counter()
+        gae = c("mnef,mnaf->ae", t2, l2, -0.5)
+        gmi = c("mnef,inef->mi", t2, l2, 0.5)
+        # the ladder L_ijab = 1/2 l_ijef W_efab: packed pairs against <vv||vv>, then the two pieces of W_abef - <vv||vv>
+        if npo and npv:
+            l2_p = be.pair_pack(be.pair_pack(l2, no * no, nv, 1), 1, no, npv)  # (i<j, e<f)
+            lad_p = be.empty((npo, npv))
+            be.gemm_raw("N", "N", npo, npv, npv, 1.0, l2_p, npv, 0, vvvv_p, npv, 0, 0.0, lad_p, npv, 0, 1)
+            lad_ab = be.pair_unpack(lad_p, npo, nv, 1)                 # (i<j, a, b)
+            be.pair_unpack(lad_ab, 1, no, nv * nv, 1.0, 0.0, lad)      # (i, j, a, b)
+            del l2_p, lad_p, lad_ab
+        else:
+            lad.zero_()
+        y = c("ijef,mf->ijem", l2, t1)
+        c("ijem,meab->ijab", y, ovvv, 1.0, lad, 1.0)
+        x = c("ijef,mnef->ijmn", l2, tau)
+        c("ijmn,mnab->ijab", x, oovv, 0.25, lad, 1.0)
+        del y, x
+        # Lambda_1
+        r1.copy_(fme)
+        c("ie,ea->ia", l1, fae, 1.0, r1, 1.0)
+        c("ma,im->ia", l1, fmi, -1.0, r1, 1.0)
+        c("me,ieam->ia", l1, wmbej, 1.0, r1, 1.0)
+        c("imef,efam->ia", l2, wabei, 0.5, r1, 1.0)
+        c("imae,me->ia", lad, t1, 1.0, r1, 1.0)
+        c("mnae,iemn->ia", l2, wmbij, -0.5, r1, 1.0)
+        c("ef,iefa->ia", gae, wmaef, 1.0, r1, 1.0)
+        c("mn,mina->ia", gmi, wmnie, -1.0, r1, 1.0)
+        # Lambda_2
+        r2.copy_(oovv)
+        be.permute4(lad, ident, 1.0, 1.0, r2)
+        c("mnab,ijmn->ijab", l2, wmnij, 0.5, r2, 1.0)
+        tmp = c("ijae,eb->ijab", l2, fae)
+        c("ijae,be->ijab", oovv, gae, 1.0, tmp, 1.0)
+        c("ma,ijmb->ijab", l1, wmnie, -1.0, tmp, 1.0)
+        be.permute4(tmp, ident, 1.0, 1.0, r2)
+        be.permute4(tmp, swap_ab, -1.0, 1.0, r2)
+        c("imab,jm->ijab", l2, fmi, 1.0, tmp, 0.0)
+        c("imab,mj->ijab", oovv, gmi, 1.0, tmp, 1.0)
+        c("ie,jeab->ijab", l1, wmaef, 1.0, tmp, 1.0)
+        be.permute4(tmp, ident, -1.0, 1.0, r2)
+        be.permute4(tmp, swap_ij, 1.0, 1.0, r2)
+        c("imae,jebm->ijab", l2, wmbej, 1.0, tmp, 0.0)
+        be.permute4(tmp, ident, 1.0, 1.0, r2)
+        be.permute4(tmp, swap_ij, -1.0, 1.0, r2)
+        be.permute4(tmp, swap_ab, -1.0, 1.0, r2)
+        be.permute4(tmp, swap_both, 1.0, 1.0, r2)
+        be.ccsd_lambda_outer(l1, fme, r2)  # P(ij) P(ab) l_ia F_jb
+        del tmp, gae, gmi
+        slot = (it - 1) % diis_space
+        be.ccsd_update(no, nv, res, lam, eo, ev, hist_l[slot], hist_e[slot], maxerr)
+        if slot in age:
+            age.remove(slot)
+        age.append(slot)
+        m = len(age)
+        row = be.dots(hist_e[slot], hist_e[:m] if m < diis_space else hist_e)
+        bmat[slot, : len(row)] = row
+        bmat[: len(row), slot] = row
+        err_max = float(be.read_scalars(maxerr)[0])
+        coef = None
+        if m > 1:
+            b = -np.ones((m + 1, m + 1))
+            b[m, m] = 0.0
+            b[:m, :m] = bmat[np.ix_(age, age)]
+            rhs = np.zeros(m + 1)
+            rhs[m] = -1.0
+            try:
+                sol = np.linalg.solve(b, rhs)[:m]
+                coef = np.zeros(m)
+                coef[age] = sol
+            except np.linalg.LinAlgError:
+                pass
+        if coef is None:
+            lam.copy_(hist_l[slot])
+        else:
+            be.lincomb(coef, hist_l[:m], out=lam)
+        cycle_seconds.append(time.perf_counter() - t_start)
+        if err_max < max(conv_tol, 1e-9) * 10:
+            converged = True
+            break
+    # ---- the density (ccsd.density_blocks), assembled and checked by nbx_ccsd_rdm1
+    xmi = c("mnef,inef->mi", l2, t2, 0.5)
+    yae = c("mnef,mnaf->ae", l2, t2, 0.5)
+    c("me,ma->ae", l1, t1, 1.0, yae, 1.0)
+    goo = c("ie,je->ij", l1, t1, -1.0)
+    c("imef,jmef->ij", l2, t2, -0.5, goo, 1.0)
+    gvv = c("ma,mb->ab", l1, t1)
+    c("mnae,mnbe->ab", l2, t2, 0.5, gvv, 1.0)
+    gvo = be.permute4(t1, [1, 0])
+    c("imae,me->ai", t2, l1, 1.0, gvo, 1.0)
+    c("mi,ma->ai", xmi, t1, -1.0, gvo, 1.0)
+    c("ie,ae->ai", t1, yae, -1.0, gvo, 1.0)
+    dm1, cross = be.ccsd_rdm1(occ, vir, goo, l1, gvo, gvv)
+    cross_h = float(be.read_scalars(cross)[0])
+    host.check_cross_spin(cross_h)
+    if stats is not None:
+        stats.update(lambda_cycle_seconds=cycle_seconds, lambda_iterations=it, lambda_setup_seconds=setup_seconds,
+                     lambda_cross_spin=cross_h)
+    return dict(l1=be.to_host(l1).copy(), l2=be.to_host(l2).copy(), lambda_converged=converged, lambda_iterations=it,
+                dm1=np.array(be.to_host(dm1), dtype=float))

@@ -547,15 +547,19 @@ class NbedDriver:
     """Run projection-based embedding and produce the embedded active-space Hamiltonian."""
 
     def __init__(self, config: NbedConfig, provider=None, backend=None, hamiltonian_format: str = "dense",
-                 ccsd_triples: bool | None = None):
+                 ccsd_triples: bool | None = None, ccsd_density: bool | None = None):
         """``hamiltonian_format``: "dense" -- ``result["second_quantised"]`` is the reference's
         ``(constant, h1 (2n,2n), h2 (2n,2n,2n,2n))``; "spatial" -- a ``SpatialHamiltonian`` (three unique
         spin blocks, 16/3 times smaller; ``.to_dense()`` gives the former).  ``ccsd_triples``: the embedded CCSD also
         reports CCSD(T) (``result["e_ccsd_t"]``, ``result["ccsd_t_emb"]``); ``None`` reads ``NBED_CCSD_TRIPLES`` = 0
-        (default) | 1."""
+        (default) | 1.  ``ccsd_density``: the embedded CCSD also solves its Lambda equations and reports the
+        one-particle density (``result["ccsd_rdm1"]``, (2, n, n) in the embedded MO basis of ``result["scf"]``, and
+        ``result["ccsd_natural_occupations"]``); ``None`` reads ``NBED_CCSD_DENSITY`` = 0 (default) | 1.  Where PySCF
+        solved, the two keys come from its ``make_rdm1()`` -- a path that needs PySCF and is not exercised without it."""
         if hamiltonian_format not in ("dense", "spatial"):
             raise NbedDriverError(f"unknown hamiltonian_format {hamiltonian_format!r}")
         self.ccsd_triples = ccsd_triples
+        self.ccsd_density = ccsd_density
         self.hamiltonian_format = hamiltonian_format
         self.config = config
         self._provider = provider
@@ -618,11 +622,15 @@ class NbedDriver:
         the device above its cap when the backend offers ``ccsd`` (``nbed_amd.ccsd_gpu``).  ``NBED_CCSD_SOLVER`` =
         ``auto`` (default) | ``host`` | ``device`` forces either of the two at any size it accepts.  With the triples
         switched on (``ccsd_triples`` / ``NBED_CCSD_TRIPLES=1``) whichever solver runs also leaves the (T) energy in
-        ``e_t``."""
+        ``e_t``; with the density switched on (``ccsd_density`` / ``NBED_CCSD_DENSITY=1``) either built-in solver runs
+        with ``density=True`` and the result offers ``rdm1()`` and ``natural_occupations()``."""
         mode = os.environ.get("NBED_CCSD_SOLVER", "auto")
         if mode not in ("auto", "host", "device"):
             raise NbedDriverError(f"NBED_CCSD_SOLVER={mode!r}: expected 'auto', 'host' or 'device'")
         triples = self._want_triples()
+        extra = {"triples": True} if triples else {}
+        if self._want_density():
+            extra["density"] = True
         try:
             cc = run_emb_ccsd(scf_obj, frozen, self.config.convergence, self.config.max_ram_memory)[0]
             if triples:
@@ -650,13 +658,9 @@ class NbedDriver:
                                       f"orbitals, the molecule {na} + {nb} electrons")
             conv_tol = min(self.config.convergence, 1e-8)
             if on_device:  # the three spatial spin blocks stay on the device; no (2n)^4 tensor anywhere
-                if triples:
-                    return self.be.ccsd(builder.build_spatial_device(), occupied, conv_tol=conv_tol, triples=True)
-                return self.be.ccsd(builder.build_spatial_device(), occupied, conv_tol=conv_tol)
+                return self.be.ccsd(builder.build_spatial_device(), occupied, conv_tol=conv_tol, **extra)
             const, h1, h2 = builder.build()
-            if triples:
-                return ccsd.solve(const, h1, h2, occupied, conv_tol=conv_tol, triples=True)
-            return ccsd.solve(const, h1, h2, occupied, conv_tol=conv_tol)
+            return ccsd.solve(const, h1, h2, occupied, conv_tol=conv_tol, **extra)
 
     def _want_triples(self) -> bool:
         """The ``ccsd_triples`` argument, or ``NBED_CCSD_TRIPLES`` = 0 (default) | 1 where it is ``None``."""
@@ -666,6 +670,26 @@ class NbedDriver:
         if flag not in ("0", "1"):
             raise NbedDriverError(f"NBED_CCSD_TRIPLES={flag!r}: expected '0' or '1'")
         return flag == "1"
+
+    def _want_density(self) -> bool:
+        """The ``ccsd_density`` argument, or ``NBED_CCSD_DENSITY`` = 0 (default) | 1 where it is ``None``."""
+        if self.ccsd_density is not None:
+            return bool(self.ccsd_density)
+        flag = os.environ.get("NBED_CCSD_DENSITY", "0")
+        if flag not in ("0", "1"):
+            raise NbedDriverError(f"NBED_CCSD_DENSITY={flag!r}: expected '0' or '1'")
+        return flag == "1"
+
+    @staticmethod
+    def _ccsd_density_of(cc):
+        """(dm1 (2, n, n), natural occupations) of a CCSD result: the built-in solvers' own ``rdm1()``, or PySCF's
+        ``make_rdm1()`` (MO basis; a spin-summed restricted density is halved into two equal spin blocks)."""
+        if hasattr(cc, "rdm1"):
+            return cc.rdm1(), cc.natural_occupations()
+        dm = np.asarray(cc.make_rdm1())
+        dm = np.stack([0.5 * dm, 0.5 * dm]) if dm.ndim == 2 else dm
+        total = dm[0] + dm[1]
+        return dm, np.linalg.eigvalsh(0.5 * (total + total.T))[::-1].copy()
 
     @cached_property
     def _global_ccsd(self):
@@ -1022,6 +1046,8 @@ class NbedDriver:
             if self._want_triples():
                 result["e_ccsd_t"] = result["e_ccsd"] + ccsd_emb.e_t
                 result["ccsd_t_emb"] = result["ccsd_emb"] + ccsd_emb.e_t
+            if self._want_density():
+                result["ccsd_rdm1"], result["ccsd_natural_occupations"] = self._ccsd_density_of(ccsd_emb)
         if cfg.run_fci_emb is True:
             fci_emb = self._run_emb_fci(result["scf"])
             result["e_fci"] = fci_emb.e_tot + self.e_env + self.two_e_cross - corr

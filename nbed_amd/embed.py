@@ -11,11 +11,13 @@ from .driver import NbedDriver
 
 
 def nbed(config: NbedConfig | str | Path | None = None, provider=None, backend=None,
-         hamiltonian_format: str = "dense", ccsd_triples: bool | None = None, **config_kwargs) -> NbedDriver:
-    """Validate the configuration, run ``NbedDriver.embed()`` and return the driver (``ccsd_triples``: as
-    ``NbedDriver``'s, not a configuration field)."""
+         hamiltonian_format: str = "dense", ccsd_triples: bool | None = None, ccsd_density: bool | None = None,
+         **config_kwargs) -> NbedDriver:
+    """Validate the configuration, run ``NbedDriver.embed()`` and return the driver (``ccsd_triples``, ``ccsd_density``:
+    as ``NbedDriver``'s, not configuration fields)."""
     driver = NbedDriver(parse_config(config, **config_kwargs), provider=provider, backend=backend,
-                        hamiltonian_format=hamiltonian_format, ccsd_triples=ccsd_triples)
+                        hamiltonian_format=hamiltonian_format, ccsd_triples=ccsd_triples,
+                        ccsd_density=ccsd_density)
     driver.embed()
     return driver
 
