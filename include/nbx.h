@@ -1063,6 +1063,32 @@ int nbx_ccsd_triples_energy(nbx_ctx* ctx, int64_t nocc, int64_t nvir, int64_t nc
                             const double* d_oovv, const double* d_eo, const double* d_ev, void* d_work,
                             size_t work_bytes, double* d_energy);
 
+/* ------------------------------------------------------------------ MP2 (csrc/mp2.hip)
+ * Second-order amplitudes and pair energy of one spin pair: what a PySCF user gets from mp.MP2 / mp.UMP2 on
+ * the embedded object the reference hands to its post-HF step (nbed/driver.py:1105-1135), in the non-canonical
+ * form over semicanonical orbitals (f_oo, f_vv diagonal per spin: d_eo*, d_ev*).  d_v is the chemist block
+ * V[i,a,j,b] = (ia|jb), row-major (no1, nv1, no2, nv2).  With d = ((eo1[i] + eo2[j]) - ev1[a]) - ev2[b],
+ * evaluated in this order,
+ *      same_spin == 0:  t = V[i,a,j,b] / d,                  energy = sum t V[i,a,j,b];
+ *      same_spin != 0:  t = (V[i,a,j,b] - V[i,b,j,a]) / d,   energy = 1/4 sum t (V[i,a,j,b] - V[i,b,j,a]),
+ * which needs nv1 == nv2 and no1 <= no2: no1 < no2 is a slice over i of the square block (rows i of V and of
+ * d_eo1 those of the slice; the sum is then the slice's share).  a == b gives an exact 0.
+ * d_t receives the amplitudes in the layout T[a, i, j, b], row-major (nv1, no1, no2, nv2), chosen so that both
+ * virtual-virtual densities are one nbx_gemm on the buffer as it stands:
+ *      D1[a,b] = sum_{ijc} t_iajc t_ibjc = T T^T   with T as (nv1) x (no1 no2 nv2):  'N','T';
+ *      D2[c,d] = sum_{aij} t_iajc t_iajd = T^T T   with T as (nv1 no1 no2) x (nv2):  'T','N'.
+ * A workgroup takes an (i, j) pair and a 32 x 32 tile of (a, b) -- nbx_mp2_pairs_tile() returns the 32 --; in
+ * the same-spin case together with its mirror tile, both read along b and exchanged through LDS.  No atomics:
+ * every workgroup writes the partial sum of the items it walked into d_work (nbx_mp2_pairs_worksize bytes, every
+ * slot written) and one workgroup adds them in a fixed order, so equal shapes and inputs give equal bits.  Any
+ * extent is legal; an empty block gives d_energy = 0 and launches nothing.  NBX_E_NOMEM for a short workspace.
+ * Does not synchronise.                                                                                   */
+size_t nbx_mp2_pairs_worksize(int64_t no1, int64_t nv1, int64_t no2, int64_t nv2, int same_spin);
+int nbx_mp2_pairs_tile(void);
+int nbx_mp2_pairs(nbx_ctx* ctx, int64_t no1, int64_t nv1, int64_t no2, int64_t nv2, const double* d_v,
+                  const double* d_eo1, const double* d_ev1, const double* d_eo2, const double* d_ev2, int same_spin,
+                  double* d_t, void* d_work, size_t work_bytes, double* d_energy);
+
 /* ------------------------------------------------------------------ full CI (csrc/fci.hip)
  * What surrounds the GEMM of a determinant FCI sigma build (nbed_amd/fci_gpu.py): the reference runs PySCF's
  * fci.FCI on the embedded object (nbed/driver.py:1044-1102); here H c is formed on the device from the three

@@ -241,6 +241,9 @@ SIGNATURES = {
     "nbx_ccsd_triples_worksize": (c_size_t, [c_int64, c_int64]),
     "nbx_ccsd_triples_tile": (c_int, []),
     "nbx_ccsd_triples_energy": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nbx_mp2_pairs_worksize": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    "nbx_mp2_pairs_tile": (c_int, []),
+    "nbx_mp2_pairs": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),
     "nbx_fci_gmat": (c_int, [_P, c_int64, _P, _P, _P]),
     "nbx_fci_gather": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
     "nbx_fci_scatter": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_double, _P, c_int, _P]),

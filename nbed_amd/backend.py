@@ -1820,6 +1820,31 @@ class HipBackend:
         self._call("nbx_ccsd_triples_energy", no, nv, ncubes, self._p(cubes), self._p(ijk), self._p(t1), self._p(fov),
                    self._p(t2), self._p(oovv), self._p(eo), self._p(ev), self._p(work), 8 * work.numel(), self._p(out))
 
+    def mp2_pairs_tile(self) -> int:
+        """Edge of the (a, b) tile of ``nbx_mp2_pairs``."""
+        return int(self.lib.nbx_mp2_pairs_tile())
+
+    def mp2_pairs(self, v, eo1, ev1, eo2, ev2, same_spin: bool):
+        """Second-order amplitudes and pair energy of the chemist block ``v[i,a,j,b]`` (no1, nv1, no2, nv2) over
+        semicanonical eigenvalues (device vectors): ``(t, energy)`` with ``t`` in the layout (nv1, no1, no2, nv2) =
+        ``t[a,i,j,b]`` and ``energy`` a device double (include/nbx.h, "MP2").  ``same_spin`` antisymmetrises; it needs
+        nv1 == nv2 and no1 <= no2 (no1 < no2: a slice over i, ``eo1`` that of the slice)."""
+        if v.dim() != 4 or not v.is_contiguous() or v.dtype != self.torch.float64:
+            raise ValueError("mp2_pairs: v must be a contiguous float64 (no1, nv1, no2, nv2) tensor")
+        no1, nv1, no2, nv2 = (int(s) for s in v.shape)
+        if eo1.numel() != no1 or ev1.numel() != nv1 or eo2.numel() != no2 or ev2.numel() != nv2:
+            raise ValueError("mp2_pairs: eigenvalue vectors do not match the block")
+        if any(e.dtype != self.torch.float64 or not e.is_contiguous() for e in (eo1, ev1, eo2, ev2)):
+            raise ValueError("mp2_pairs: eigenvalue vectors must be contiguous float64")
+        if same_spin and (nv1 != nv2 or no1 > no2):
+            raise ValueError("mp2_pairs: a same-spin block is (no1 <= no2, nv, no2, nv)")
+        same = int(bool(same_spin))
+        t, energy = self.empty((nv1, no1, no2, nv2)), self.empty(1)
+        work = self.empty(max(1, int(self.lib.nbx_mp2_pairs_worksize(no1, nv1, no2, nv2, same)) // 8))
+        self._call("nbx_mp2_pairs", no1, nv1, no2, nv2, self._p(v), self._p(eo1), self._p(ev1), self._p(eo2), self._p(ev2),
+                   same, self._p(t), self._p(work), 8 * work.numel(), self._p(energy))
+        return t, energy
+
     def ccsd(self, spatial, occupied, **kwargs):
         """Spin-orbital CCSD on the device (``nbed_amd.ccsd_gpu.solve_spatial``): the capability the driver asks for;
         ``triples=True`` adds the (T) energy as ``e_t``, ``density=True`` the Lambda amplitudes and ``rdm1()``."""

@@ -547,8 +547,17 @@ class NbedDriver:
     """Run projection-based embedding and produce the embedded active-space Hamiltonian."""
 
     def __init__(self, config: NbedConfig, provider=None, backend=None, hamiltonian_format: str = "dense",
-                 ccsd_triples: bool | None = None, ccsd_density: bool | None = None):
-        """``hamiltonian_format``: "dense" -- ``result["second_quantised"]`` is the reference's
+                 ccsd_triples: bool | None = None, ccsd_density: bool | None = None, mp2: bool | None = None,
+                 fno_virtuals: int | None = None, fno_threshold: float | None = None):
+        """``mp2``: the embedded MP2 energy (``result["e_mp2"]``, ``result["mp2_emb"]``, composed as the CCSD keys
+        are; ``nbed_amd.mp2.solve_scf``); ``None`` reads ``NBED_MP2`` = 0 (default) | 1.  ``fno_virtuals`` = k /
+        ``fno_threshold`` = an occupation: after the virtual localisation ``result["scf"]`` is truncated to its
+        canonicalised MP2 natural virtual orbitals (``nbed_amd.mp2.frozen_natural_orbitals``: k dropped per spin, or
+        those below the threshold), ``result["fno"]`` is its info dict, everything downstream is that of the truncated
+        space and the MP2 keys (set too) refer to the full virtual space; ``None`` reads ``NBED_FNO_VIRTUALS`` /
+        ``NBED_FNO_THRESHOLD`` (unset, or k = 0: off).  Giving both selectors is an error.
+
+        ``hamiltonian_format``: "dense" -- ``result["second_quantised"]`` is the reference's
         ``(constant, h1 (2n,2n), h2 (2n,2n,2n,2n))``; "spatial" -- a ``SpatialHamiltonian`` (three unique
         spin blocks, 16/3 times smaller; ``.to_dense()`` gives the former).  ``ccsd_triples``: the embedded CCSD also
         reports CCSD(T) (``result["e_ccsd_t"]``, ``result["ccsd_t_emb"]``); ``None`` reads ``NBED_CCSD_TRIPLES`` = 0
@@ -560,6 +569,9 @@ class NbedDriver:
             raise NbedDriverError(f"unknown hamiltonian_format {hamiltonian_format!r}")
         self.ccsd_triples = ccsd_triples
         self.ccsd_density = ccsd_density
+        self.mp2 = mp2
+        self.fno_virtuals = fno_virtuals
+        self.fno_threshold = fno_threshold
         self.hamiltonian_format = hamiltonian_format
         self.config = config
         self._provider = provider
@@ -679,6 +691,45 @@ class NbedDriver:
         if flag not in ("0", "1"):
             raise NbedDriverError(f"NBED_CCSD_DENSITY={flag!r}: expected '0' or '1'")
         return flag == "1"
+
+    def _want_mp2(self) -> bool:
+        """The ``mp2`` argument, or ``NBED_MP2`` = 0 (default) | 1 where it is ``None``."""
+        if self.mp2 is not None:
+            return bool(self.mp2)
+        flag = os.environ.get("NBED_MP2", "0")
+        if flag not in ("0", "1"):
+            raise NbedDriverError(f"NBED_MP2={flag!r}: expected '0' or '1'")
+        return flag == "1"
+
+    def _fno_selector(self) -> dict:
+        """``{}`` (FNO off), ``{"n_frozen_virt": k}`` or ``{"threshold": x}``: the ``fno_virtuals`` / ``fno_threshold``
+        arguments, or ``NBED_FNO_VIRTUALS`` / ``NBED_FNO_THRESHOLD`` where an argument is ``None``."""
+        k, thr = self.fno_virtuals, self.fno_threshold
+        if k is None and "NBED_FNO_VIRTUALS" in os.environ:
+            k = os.environ["NBED_FNO_VIRTUALS"]
+        if thr is None and "NBED_FNO_THRESHOLD" in os.environ:
+            thr = os.environ["NBED_FNO_THRESHOLD"]
+        if k is not None and thr is not None:
+            raise NbedDriverError("fno_virtuals and fno_threshold (NBED_FNO_VIRTUALS / NBED_FNO_THRESHOLD) exclude each other")
+        if k is not None:
+            try:
+                if isinstance(k, bool) or (isinstance(k, float) and k != int(k)):
+                    raise ValueError
+                k = int(k)
+            except (TypeError, ValueError):
+                raise NbedDriverError(f"fno_virtuals / NBED_FNO_VIRTUALS = {k!r}: expected a non-negative integer") from None
+            if k < 0:
+                raise NbedDriverError(f"fno_virtuals / NBED_FNO_VIRTUALS = {k!r}: expected a non-negative integer")
+            return {"n_frozen_virt": k} if k else {}  # (0: nothing to drop, the virtual space is left as it is)
+        if thr is not None:
+            try:
+                thr = float(thr)
+            except (TypeError, ValueError):
+                raise NbedDriverError(f"fno_threshold / NBED_FNO_THRESHOLD = {thr!r}: expected a number in [0, 1]") from None
+            if not 0.0 <= thr <= 1.0:
+                raise NbedDriverError(f"fno_threshold / NBED_FNO_THRESHOLD = {thr!r}: expected a number in [0, 1]")
+            return {"threshold": thr}
+        return {}
 
     @staticmethod
     def _ccsd_density_of(cc):
@@ -1038,6 +1089,18 @@ class NbedDriver:
         corr = result["correction"] + result["beta_correction"]
         result["e_rhf"] = result["scf"].e_tot + self.e_env + self.two_e_cross - corr
         result["classical_energy"] = self.e_env + self.two_e_cross + self.e_nuc - corr
+
+        fno = self._fno_selector()
+        if fno or self._want_mp2():
+            from . import mp2 as mp2_mod
+
+            if fno:  # everything below is that of the truncated space; the MP2 keys stay those of the full one
+                result["scf"], result["fno"] = mp2_mod.frozen_natural_orbitals(result["scf"], backend=be, **fno)
+                mp2_emb = result["fno"]["mp2"]
+            else:
+                mp2_emb = mp2_mod.solve_scf(result["scf"], backend=be)
+            result["e_mp2"] = mp2_emb.e_tot + self.e_env + self.two_e_cross - corr
+            result["mp2_emb"] = mp2_emb.e_tot - self.e_nuc
 
         if cfg.run_ccsd_emb is True:
             ccsd_emb, _ = self._run_emb_ccsd(result["scf"])

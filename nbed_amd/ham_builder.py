@@ -71,7 +71,15 @@ class HamiltonianBuilder:
     """Class to build molecular hamiltonians."""
 
     def __init__(self, scf_method, constant_e_shift: float = 0, n_frozen_core: int = 0, n_frozen_virt: int = 0,
-                 backend=None, shards: Shards | None = None) -> None:
+                 backend=None, shards: Shards | None = None, virtual_selection: str = "order") -> None:
+        """``virtual_selection``: which ``n_frozen_virt`` virtuals go -- "order": the last columns
+        (``reduce_virtuals``, the reference's); "fno": the MP2 natural virtual orbitals of least occupation
+        (``nbed_amd.mp2.frozen_natural_orbitals``; its ``info`` is left in ``self.fno``, and the constant is NOT
+        shifted by its ``e_correction``)."""
+        if virtual_selection not in ("order", "fno"):
+            raise HamiltonianBuilderError(f"unknown virtual_selection {virtual_selection!r}: expected 'order' or 'fno'")
+        self.virtual_selection = virtual_selection
+        self.fno = None
         self.scf_method = scf_method
         self.constant_e_shift = constant_e_shift
         self.n_frozen_core = n_frozen_core
@@ -85,6 +93,15 @@ class HamiltonianBuilder:
             self.occupancy = np.vstack((self.scf_method.mo_occ[0], self.scf_method.mo_occ[1]))
         else:
             raise HamiltonianBuilderError("occupancy dimension error")
+
+    def _reduced_scf(self):
+        """The SCF object without ``n_frozen_virt`` of its virtuals, chosen as ``virtual_selection`` says."""
+        if self.virtual_selection == "fno" and self.n_frozen_virt > 0:
+            from .mp2 import frozen_natural_orbitals
+
+            reduced, self.fno = frozen_natural_orbitals(self.scf_method, n_frozen_virt=self.n_frozen_virt, backend=self.be)
+            return reduced
+        return reduce_virtuals(self.scf_method, self.n_frozen_virt)
 
     # ------------------------------------------------------------------ one body
     @property
@@ -229,7 +246,7 @@ class HamiltonianBuilder:
         """``(constant, one_body, two_body)`` of ``build_spatial()`` left on the device: what a consumer that
         runs there (``nbed_amd.ccsd_gpu.solve_spatial``) reads without a round trip through the host."""
         if self.n_frozen_virt != 0:
-            self.scf_method = reduce_virtuals(self.scf_method, self.n_frozen_virt)
+            self.scf_method = self._reduced_scf()
         be = self.be
         one = be.asarray(self._one_body_integrals)
         be.threshold_scale(one, EQ_TOLERANCE, 1.0)
@@ -240,7 +257,7 @@ class HamiltonianBuilder:
     def build(self) -> tuple[float, np.ndarray, np.ndarray]:
         """Second-quantised fermionic Hamiltonian: (constant, h1, 0.5 * h2)."""
         if self.n_frozen_virt != 0:
-            self.scf_method = reduce_virtuals(self.scf_method, self.n_frozen_virt)
+            self.scf_method = self._reduced_scf()
         be = self.be
         logger.info("Building Hamiltonian")
         one = be.asarray(self._one_body_integrals)
