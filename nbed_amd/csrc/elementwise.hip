@@ -90,13 +90,22 @@ __global__ void fock_uhf_kernel(const double* __restrict__ h, int h3d, const dou
 
 // Hz = -kappa (F DS + (F DS)^T) and F' = F + Hz in ONE launch (the product and its symmetrisation
 // were a GEMM and an element-wise kernel: one launch less on the SCF's critical path).  One
-// wavefront per pair of 16 x 16 tiles (I, J <= I): T1 = F[I,:] DS[:,J] and T2 = F[J,:] DS[:,I] on the
-// matrix cores (k-slot order of gemm_small_kernel), Hz[I,J] = -kappa (T1 + T2^T) and its mirror image
-// through a 16 x 17 LDS tile.  Out of place: every workgroup reads all of F.
+// workgroup of TWO wavefronts per pair of 16 x 16 tiles (I, J <= I): wave 0 forms T1 = F[I,:] DS[:,J],
+// wave 1 forms T2 = F[J,:] DS[:,I] on the matrix cores (k-slot order of gemm_small_kernel), Hz[I,J] =
+// -kappa (T1 + T2^T) and its mirror image through a 16 x 17 LDS tile.  Out of place: every workgroup reads all of F.
+//
+// Why two waves.  The two products are independent chains of ceil(N / 4) dependent MFMAs each, and one
+// v_mfma_f64_16x16x4 issues per ~143 cycles (60 ns) with a wave alone on its SIMD (profiles/r03/fp64_rate_probe.txt):
+// on ONE wavefront the 74 MFMAs of N = 148 were 4.4 us of serial matrix-core time; on two SIMDs they are 2.2 us.
+// Each wave then holds two operand arrays instead of four, so the trip doubles to HZ_STEPS = 40 steps and N <= 160
+// is ONE trip to L2 (it was two).  The F elements the epilogue adds are requested in that same trip.
+// On diagonal tiles T2 = T1: wave 0 puts its own product into the LDS tile and wave 1 only keeps the barriers.
+// Same k order, same MFMAs per accumulator, the same additions: bitwise the same result.
 typedef double ew_v4f64 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(64) void huzinaga_fused_kernel(const double* __restrict__ F,
-                                                            const double* __restrict__ DS, int N, double kappa,
-                                                            double* __restrict__ hz, double* __restrict__ fock_out) {
+constexpr int HZ_STEPS = 40;
+__global__ __launch_bounds__(128) void huzinaga_fused_kernel(const double* __restrict__ F,
+                                                             const double* __restrict__ DS, int N, double kappa,
+                                                             double* __restrict__ hz, double* __restrict__ fock_out) {
     __shared__ double t2[16][17], hv[16][17];
     const int ti = blockIdx.y, tj = blockIdx.x;
     if (tj > ti) return;
@@ -105,67 +114,68 @@ __global__ __launch_bounds__(64) void huzinaga_fused_kernel(const double* __rest
     DS += blockIdx.z * n2;
     hz += blockIdx.z * n2;
     if (fock_out != nullptr) fock_out += blockIdx.z * n2;
-    const int lane = threadIdx.x, fr = lane & 15, fk = lane >> 4;
-    const int ri = ti * 16 + fr, rj = tj * 16 + fr;  // A-fragment rows of the two products = B-fragment columns
-    const bool oki = ri < N, okj = rj < N;
-    const double* fi = F + (int64_t)(oki ? ri : 0) * N;  // row ri of F (k contiguous)
-    const double* fj = F + (int64_t)(okj ? rj : 0) * N;
-    const double* dsj = DS + (okj ? rj : 0);  // column rj of DS (k strided by N)
-    const double* dsi = DS + (oki ? ri : 0);
-    ew_v4f64 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, fr = lane & 15, fk = lane >> 4;
     const bool diag = ti == tj;
-    // The operands of HZ_STEPS MFMA steps (4 k each) are requested in ONE trip to L2 -- N = 148 is two trips -- where a
-    // 16-wide k loop waited out a memory latency per trip: ten of them, the whole 11.6 us this kernel took on the SCF's
-    // critical path (the anti-pattern gemm_small_kernel was written to avoid).  One wavefront per workgroup: the
-    // 4 x HZ_STEPS operand registers are there.  Same k order, same MFMAs: bitwise the same result.
-    constexpr int HZ_STEPS = 20;
-    for (int k0 = 0; k0 < N; k0 += 4 * HZ_STEPS) {
-        double a1[HZ_STEPS], b1[HZ_STEPS], a2[HZ_STEPS], b2[HZ_STEPS];
+    const bool work = wv == 0 || !diag;  // (uniform per wave)
+    // this wave's product: rows ta of F times columns tb of DS; it stores the tile (ta, tb) of Hz
+    const int ta = wv == 0 ? ti : tj, tb = wv == 0 ? tj : ti;
+    const int ra = ta * 16 + fr, cb = tb * 16 + fr;  // A-fragment row, B-fragment column
+    const bool oka = ra < N, okb = cb < N;
+    const double* fa = F + (int64_t)(oka ? ra : 0) * N;  // row ra of F (k contiguous)
+    const double* db = DS + (okb ? cb : 0);              // column cb of DS (k strided by N)
+    ew_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+    // accumulator element r of a lane: tile row fk + 4 r, tile column fr -- where this wave stores
+    double fo[4];
+    int64_t oo[4];
+    bool oin[4];
 #pragma unroll
-        for (int j = 0; j < HZ_STEPS; ++j) {
-            const int k = k0 + 4 * j + fk;
-            const bool in = k < N;
-            a1[j] = (in && oki) ? fi[k] : 0.0;
-            b1[j] = (in && okj) ? dsj[(int64_t)k * N] : 0.0;
-            a2[j] = (in && okj && !diag) ? fj[k] : 0.0;
-            b2[j] = (in && oki && !diag) ? dsi[(int64_t)k * N] : 0.0;
-        }
+    for (int r = 0; r < 4; ++r) {
+        const int row = ta * 16 + fk + 4 * r, col = tb * 16 + fr;
+        oin[r] = work && row < N && col < N;
+        oo[r] = oin[r] ? (int64_t)row * N + col : 0;
+        fo[r] = fock_out != nullptr ? F[oo[r]] : 0.0;
+    }
+    if (work) {
+        for (int k0 = 0; k0 < N; k0 += 4 * HZ_STEPS) {
+            // (unconditional loads from addresses clamped into the matrix, masked afterwards: a load under a per-lane
+            //  condition becomes a branch of its own)
+            double a[HZ_STEPS], b[HZ_STEPS];
 #pragma unroll
-        for (int j = 0; j < HZ_STEPS; ++j) {
-            if (k0 + 4 * j < N) {  // uniform (steps past N would multiply zeros; the old loop ran to the next multiple of 16)
-                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[j], b1[j], acc1, 0, 0, 0);
-                if (!diag) acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2[j], b2[j], acc2, 0, 0, 0);
+            for (int j = 0; j < HZ_STEPS; ++j) {
+                const int k = k0 + 4 * j + fk, kc = k < N ? k : N - 1;
+                a[j] = fa[kc];
+                b[j] = db[(int64_t)kc * N];
+            }
+#pragma unroll
+            for (int j = 0; j < HZ_STEPS; ++j) {
+                const bool in = k0 + 4 * j + fk < N;
+                if (k0 + 4 * j < N)  // uniform (steps past N would multiply zeros; the first loop ran to the next multiple of 16)
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((in && oka) ? a[j] : 0.0, (in && okb) ? b[j] : 0.0, acc, 0, 0, 0);
             }
         }
     }
-    if (diag) acc2 = acc1;
-    // accumulator element r of a lane: tile row fk + 4 r, tile column fr
+    // T2 (on a diagonal tile: T1 itself) goes to LDS
+    if (wv == (diag ? 0 : 1)) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) t2[fk + 4 * r][fr] = acc2[r];
-    __syncthreads();
-    double val[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        val[r] = -kappa * (acc1[r] + t2[fr][fk + 4 * r]);  // T1[i][j] + T2[j][i]
-        hv[fk + 4 * r][fr] = val[r];
+        for (int r = 0; r < 4; ++r) t2[fk + 4 * r][fr] = acc[r];
     }
     __syncthreads();
+    double val[4] = {0.0, 0.0, 0.0, 0.0};
+    if (wv == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            val[r] = -kappa * (acc[r] + t2[fr][fk + 4 * r]);  // T1[i][j] + T2[j][i]
+            hv[fk + 4 * r][fr] = val[r];
+        }
+    }
+    __syncthreads();
+    // wave 0 stores the tile (I, J), wave 1 its mirror image Hz[J rows][I columns], element [j][i] = value of [i][j]
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int row = ti * 16 + fk + 4 * r, col = tj * 16 + fr;
-        if (row < N && col < N) {
-            const int64_t o = (int64_t)row * N + col;
-            hz[o] = val[r];
-            if (fock_out != nullptr) fock_out[o] = F[o] + val[r];
-        }
-        if (!diag) {  // the mirror tile: Hz[J rows][I columns], element [j][i] = value of [i][j]
-            const int mrow = tj * 16 + fk + 4 * r, mcol = ti * 16 + fr;
-            if (mrow < N && mcol < N) {
-                const int64_t o = (int64_t)mrow * N + mcol;
-                const double v = hv[fr][fk + 4 * r];
-                hz[o] = v;
-                if (fock_out != nullptr) fock_out[o] = F[o] + v;
-            }
+        if (oin[r]) {
+            const double v = wv == 0 ? val[r] : hv[fr][fk + 4 * r];
+            hz[oo[r]] = v;
+            if (fock_out != nullptr) fock_out[oo[r]] = fo[r] + v;
         }
     }
 }
@@ -1256,7 +1266,7 @@ int nbx_huzinaga_fused(nbx_ctx* ctx, int64_t nao, int64_t batch, const double* d
     NBX_CHECK_ARG(ctx && d_f && d_ds && d_hz && nao > 0 && batch > 0 && batch < 65536);
     NBX_CHECK_ARG(d_fock_out != d_f);  // every workgroup reads all of F: the update is out of place
     const unsigned g = (unsigned)nbx_cdiv(nao, 16);
-    hipLaunchKernelGGL(huzinaga_fused_kernel, dim3(g, g, (unsigned)batch), dim3(64), 0, ctx->stream, d_f, d_ds,
+    hipLaunchKernelGGL(huzinaga_fused_kernel, dim3(g, g, (unsigned)batch), dim3(128), 0, ctx->stream, d_f, d_ds,
                        (int)nao, kappa, d_hz, d_fock_out);
     NBX_LAUNCH_CHECK();
     return NBX_OK;
