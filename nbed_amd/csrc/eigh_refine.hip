@@ -48,6 +48,15 @@ constexpr double RF_CLUSTER_NOISE = 1.0e-14;
 // max|E| ~ 1e-7..1e-6, the accuracy any backward-stable solver (LAPACK's dsygvd in the reference) reaches on them.
 // For matrices of ordinary norm the test is stricter than RF_TOL and changes nothing.
 constexpr double RF_NOISE = 8.0 * 1.1102230246251565e-16;
+// ... but the update X (I + E) is first order: with E antisymmetric up to R it costs (I + E)^T (I + E) - I = -E^2 of
+// orthonormality, (E^2)_ii = sum_k E_ik^2.  Noise divided by a gap of 1e-10 .. 1e-12 ||A|| (a close pair, a triple
+// spaced by 1e-13 ||A||) is an E of 1e-5 .. 1e-3, and a matrix accepted "at noise" with it was delivered with
+// |V^T V - I| up to 4e-7.  nbx_eigh_refine therefore takes the noise exit only below RF_NOISE_EMAX: three partners
+// at 5e-7 cost a level 0.75e-12, what the Newton-Schulz step of the cold route leaves (eigh_tridiag.hip: a Gram defect
+// of 1e-6 squared); above it the matrix goes to the Jacobi fallback, which rotates such pairs exactly.  The stalled
+// mu-shifted matrices sit at 1e-7.  nbx_geig_refine, which has no fallback behind it, keeps RF_NOISE_EMAX_PENCIL.
+constexpr double RF_NOISE_EMAX = 5.0e-7;
+constexpr double RF_NOISE_EMAX_PENCIL = 1.0e-3;
 constexpr int RF_PART = 6;  // doubles each workgroup publishes per matrix
 
 // G = X^T X, S = X^T A X  ->  Ep = I + E, lambda, status.  RF_WGS workgroups per matrix (grid
@@ -274,7 +283,9 @@ __global__ __launch_bounds__(RF_THREADS) void refine_e_kernel(int N, const doubl
                 cmax = fmax(cmax, peek(part + w * RF_PART + 4));
                 nmax = fmax(nmax, peek(part + w * RF_PART + 5));
             }
-            const bool at_noise = nmax <= RF_NOISE * sqrt((double)N) * na && emax < 1.0e-3;
+            // (A == nullptr: the pencil, nbx_geig_refine)
+            const bool at_noise = nmax <= RF_NOISE * sqrt((double)N) * na &&
+                                  emax < (A != nullptr ? RF_NOISE_EMAX : RF_NOISE_EMAX_PENCIL);
             int st = 0;
             if (!(emax < RF_GIVE_UP)) st = -1;  // also NaN
             else if ((emax < RF_TOL || at_noise) && cmax <= RF_CLUSTER_NOISE * na) st = iter + 1;
