@@ -1174,78 +1174,80 @@ class HipBackend:
                    self._p(out), self._p(dout))
         return out, dout
 
+    # The three passes of the XC quadrature (csrc/xc.hip).  Each has a tau form for the meta-GGAs behind an entry point
+    # of its own; the private helpers allocate, take the workspace and call, the public methods name the entry point.
+    # (Straight-line on purpose: the functional pass takes 40 us, and a microsecond of argument packing here shows.)
+    def _xc_rho(self, entry: str, ao, dao, dm, with_tau: bool):
+        g, nao, p = int(ao.shape[0]), int(ao.shape[1]), self._p
+        rho, grad = self.empty((2, g)), self.empty((2, 3, g))
+        if not with_tau:
+            self._call(entry, g, nao, p(ao), p(dao), p(dm), p(rho), p(grad))
+            return rho, grad
+        tau = self.empty((2, g))
+        self._call(entry, g, nao, p(ao), p(dao), p(dm), p(rho), p(grad), p(tau))
+        return rho, grad, tau
+
+    def _xc_functional(self, entry: str, lead: tuple, rho, grad, tau, w, rho_floor: float):
+        """``lead``: what the entry point takes before the number of points, (code,) or (code, omega); ``tau`` is None
+        except for a meta-GGA, which returns ``vt`` as well."""
+        g, p = int(rho.shape[-1]), self._p
+        vr, vec, sums = self.empty((2, g)), self.empty((2, 3, g)), self.empty(2)
+        work = self._workspace("xc_fn", int(self.lib.nbx_xc_functional_worksize(g)))
+        if tau is None:
+            self._call(entry, *lead, g, p(rho), p(grad), p(w), float(rho_floor), p(vr), p(vec), p(sums), p(work), work.numel())
+            return vr, vec, sums
+        vt = self.empty((2, g))
+        self._call(entry, *lead, g, p(rho), p(grad), p(tau), p(w), float(rho_floor), p(vr), p(vec), p(vt), p(sums), p(work),
+                   work.numel())
+        return vr, vec, vt, sums
+
+    def _xc_vmat(self, entry: str, ao, dao, vr, vec, vt):
+        """``vt`` is None except in the tau form; both forms take the same workspace."""
+        g, nao, p = int(ao.shape[0]), int(ao.shape[1]), self._p
+        out = self.empty((2, nao, nao))
+        work = self._workspace("xc_vmat", int(self.lib.nbx_xc_vmat_worksize(g, nao)))
+        if vt is None:
+            self._call(entry, g, nao, p(ao), p(dao), p(vr), p(vec), p(out), p(work), work.numel())
+        else:
+            self._call(entry, g, nao, p(ao), p(dao), p(vr), p(vec), p(vt), p(out), p(work), work.numel())
+        return out
+
     def xc_rho(self, ao, dao, dm):
         """Spin densities (2, G) and their gradients (2, 3, G) on the grid from the stored AO values ``ao`` (G, nao),
         gradients ``dao`` (3, G, nao) and a symmetric two-spin density matrix (nbx_xc_rho: c = ao D on the matrix
         cores, reduced against ao / dao in the epilogue; both spins in one pass)."""
-        g, nao = int(ao.shape[0]), int(ao.shape[1])
-        rho, grad = self.empty((2, g)), self.empty((2, 3, g))
-        self._call("nbx_xc_rho", g, nao, self._p(ao), self._p(dao), self._p(dm), self._p(rho), self._p(grad))
-        return rho, grad
-
-    def xc_functional(self, code: int, rho, grad, w, rho_floor: float):
-        """Weighted first derivatives of the exchange-correlation energy density on the grid (nbx_xc_functional,
-        analytic): ``(vr (2, G), vec (2, 3, G), sums)`` with ``sums`` a device pair (E_xc, integrated electrons)."""
-        g = int(rho.shape[-1])
-        vr, vec, sums = self.empty((2, g)), self.empty((2, 3, g)), self.empty(2)
-        nbytes = int(self.lib.nbx_xc_functional_worksize(g))
-        work = self._workspace("xc_fn", nbytes)
-        self._call("nbx_xc_functional", int(code), g, self._p(rho), self._p(grad), self._p(w), float(rho_floor), self._p(vr),
-                   self._p(vec), self._p(sums), self._p(work), work.numel())
-        return vr, vec, sums
-
-    def xc_functional_rs(self, code: int, omega: float, rho, grad, w, rho_floor: float):
-        """``xc_functional`` for the semi-local part of a range-separated hybrid (nbx_xc_functional_rs: ``code`` from
-        ``_nbx.XC_RS_CODES``, ``omega`` the range separation of its short-range B88 exchange)."""
-        g = int(rho.shape[-1])
-        vr, vec, sums = self.empty((2, g)), self.empty((2, 3, g)), self.empty(2)
-        nbytes = int(self.lib.nbx_xc_functional_worksize(g))
-        work = self._workspace("xc_fn", nbytes)
-        self._call("nbx_xc_functional_rs", int(code), float(omega), g, self._p(rho), self._p(grad), self._p(w),
-                   float(rho_floor), self._p(vr), self._p(vec), self._p(sums), self._p(work), work.numel())
-        return vr, vec, sums
-
-    def xc_vmat(self, ao, dao, vr, vec):
-        """v_xc (2, nao, nao), symmetrised, from the weighted derivatives of ``xc_functional`` (nbx_xc_vmat: the
-        ``half`` factor is built on the fly as an operand of the product)."""
-        g, nao = int(ao.shape[0]), int(ao.shape[1])
-        out = self.empty((2, nao, nao))
-        nbytes = int(self.lib.nbx_xc_vmat_worksize(g, nao))
-        work = self._workspace("xc_vmat", nbytes)
-        self._call("nbx_xc_vmat", g, nao, self._p(ao), self._p(dao), self._p(vr), self._p(vec), self._p(out), self._p(work),
-                   work.numel())
-        return out
+        return self._xc_rho("nbx_xc_rho", ao, dao, dm, False)
 
     def xc_rho_tau(self, ao, dao, dm):
         """``xc_rho`` plus the kinetic-energy densities tau (2, G) = 1/2 sum_a diag(dao_a D dao_a^T) (nbx_xc_rho_tau: the
         slab of D staged once per column tile and multiplied by the fragments of ao and of each dao_a; ``rho`` and
         ``grad`` are ``xc_rho``'s bit for bit)."""
-        g, nao = int(ao.shape[0]), int(ao.shape[1])
-        rho, grad, tau = self.empty((2, g)), self.empty((2, 3, g)), self.empty((2, g))
-        self._call("nbx_xc_rho_tau", g, nao, self._p(ao), self._p(dao), self._p(dm), self._p(rho), self._p(grad), self._p(tau))
-        return rho, grad, tau
+        return self._xc_rho("nbx_xc_rho_tau", ao, dao, dm, True)
+
+    def xc_functional(self, code: int, rho, grad, w, rho_floor: float):
+        """Weighted first derivatives of the exchange-correlation energy density on the grid (nbx_xc_functional,
+        analytic): ``(vr (2, G), vec (2, 3, G), sums)`` with ``sums`` a device pair (E_xc, integrated electrons)."""
+        return self._xc_functional("nbx_xc_functional", (int(code),), rho, grad, None, w, rho_floor)
+
+    def xc_functional_rs(self, code: int, omega: float, rho, grad, w, rho_floor: float):
+        """``xc_functional`` for the semi-local part of a range-separated hybrid (nbx_xc_functional_rs: ``code`` from
+        ``_nbx.XC_RS_CODES``, ``omega`` the range separation of its short-range B88 exchange)."""
+        return self._xc_functional("nbx_xc_functional_rs", (int(code), float(omega)), rho, grad, None, w, rho_floor)
 
     def xc_functional_mgga(self, code: int, rho, grad, tau, w, rho_floor: float):
         """``xc_functional`` for a meta-GGA (nbx_xc_functional_mgga: ``code`` from ``_nbx.XC_MGGA_CODES``):
         ``(vr (2, G), vec (2, 3, G), vt (2, G) = w dE/dtau, sums)``."""
-        g = int(rho.shape[-1])
-        vr, vec, vt, sums = self.empty((2, g)), self.empty((2, 3, g)), self.empty((2, g)), self.empty(2)
-        nbytes = int(self.lib.nbx_xc_functional_worksize(g))
-        work = self._workspace("xc_fn", nbytes)
-        self._call("nbx_xc_functional_mgga", int(code), g, self._p(rho), self._p(grad), self._p(tau), self._p(w),
-                   float(rho_floor), self._p(vr), self._p(vec), self._p(vt), self._p(sums), self._p(work), work.numel())
-        return vr, vec, vt, sums
+        return self._xc_functional("nbx_xc_functional_mgga", (int(code),), rho, grad, tau, w, rho_floor)
+
+    def xc_vmat(self, ao, dao, vr, vec):
+        """v_xc (2, nao, nao), symmetrised, from the weighted derivatives of ``xc_functional`` (nbx_xc_vmat: the
+        ``half`` factor is built on the fly as an operand of the product)."""
+        return self._xc_vmat("nbx_xc_vmat", ao, dao, vr, vec, None)
 
     def xc_vmat_tau(self, ao, dao, vr, vec, vt):
         """``xc_vmat`` with sum_a dao_a^T (vt / 4 dao_a) added before the symmetrisation (nbx_xc_vmat_tau: after it,
         1/2 int v_tau grad phi_m . grad phi_n)."""
-        g, nao = int(ao.shape[0]), int(ao.shape[1])
-        out = self.empty((2, nao, nao))
-        nbytes = int(self.lib.nbx_xc_vmat_tau_worksize(g, nao))
-        work = self._workspace("xc_vmat", nbytes)
-        self._call("nbx_xc_vmat_tau", g, nao, self._p(ao), self._p(dao), self._p(vr), self._p(vec), self._p(vt), self._p(out),
-                   self._p(work), work.numel())
-        return out
+        return self._xc_vmat("nbx_xc_vmat_tau", ao, dao, vr, vec, vt)
 
     def ao_table(self, basis):
         """The shells of an ``integrals.Basis`` flattened into the device arrays nbx_eval_ao reads."""

@@ -2,21 +2,26 @@
 // reference gets from PySCF's numint + libxc behind `dft.UKS.get_veff` (nbed/driver.py:155-191 global Kohn-Sham,
 // :315-431 `_subsystem_dft`, :845-852 the embedding potential, :1138-1231 DFT-in-DFT).  One evaluation of
 // (E_xc, v_xc) for a two-spin density matrix is three kernels over the stored AO values ao (G, nao) and gradients
-// dao (3, G, nao) of the molecular grid (grid.hip makes them):
+// dao (3, G, nao) of the molecular grid (grid.hip makes them).  Each kernel has a tau form for the meta-GGAs (TPSS,
+// TPSSh), which carries the kinetic-energy density tau_x = 1/2 sum_i |grad psi_i|^2 through the same body: a template
+// parameter, so the plain instantiations hold none of it.
 //
 //   xc_rho_kernel      c = ao D on the matrix cores (v_mfma_f64_16x16x4_f64), tile by tile, BOTH spins from one pass
 //                      over ao; the tile never leaves the registers: rho = sum_m c ao and grad rho = 2 sum_m c dao
 //                      are reduced in the epilogue (dao is read exactly once)                      -- MFMA bound
+//                      TAU: three more products per tile, dao_a D against dao_a: tau = 1/2 sum_a sum_m (dao_a D) dao_a
 //   xc_functional_kernel  one thread per grid point: energy density and its first derivatives with respect to
 //                      (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb) written out analytically (Slater, Becke 88,
 //                      VWN-RPA / VWN5, LYP in Miehlich's form: libxc's B3LYP = 0.08 S + 0.72 B88 + 0.19 VWN_RPA +
 //                      0.81 LYP + 0.2 HF, B3LYP5 with VWN5, BLYP; PBE exchange, Perdew-Wang 1992 and PBE
 //                      correlation: PBE, PBEH), one instantiation per functional, quadrature weights folded in, E_xc
 //                      and the electron count reduced in a fixed order                              -- ALU (exp, log, cbrt)
+//                      the TPSS codes read tau and write the derivative with respect to it as well
 //   xc_vmat_kernel     v[m][n] = sum_g ao[g][m] half[g][n],  half = v_rho / 2 ao + (2 v_ss grad rho_s + v_ab grad
 //                      rho_o) . dao, with `half` built ON THE FLY as the B operand (it never exists in memory), split
 //                      over chunks of grid points; xc_vmat_reduce_kernel adds the chunks in a fixed order and
 //                      symmetrises (v + v^T)                                                        -- MFMA bound
+//                      TAU: + sum_a dao_a[g][m] (v_tau / 4 dao_a)[g][n], three more operands per step of grid points
 #include "nbx_common.h"
 
 namespace {
@@ -28,10 +33,16 @@ typedef double xc_v4 __attribute__((ext_vector_type(4)));
 // c = ao D: the (nao x 16) slab of D (both spins) goes to LDS once per workgroup; A fragments ao[g][k] are kept
 // in registers across the column tiles when nao <= 4 AREG.  C layout of the 16x16x4 product: acc[r] of lane
 // (fk = lane >> 4, fr = lane & 15) is element (row fk + 4 r, column fr).
-template <int AREG>
+// TAU (`tau` is written by no other instantiation; null there): after c = ao D the slab of D that is already in LDS is multiplied by
+// the fragments of dao_x, dao_y and dao_z in turn (streamed: 3 x 40 doubles would not fit beside the ao fragments), and
+// each product is reduced against the dao_a values the epilogue of rho has just read.  The passes are sequential inside
+// the tile loop, two accumulators live at a time; rho and grad rho are the plain kernel's bit for bit (same fragments,
+// same order, same epilogue).                                                                -- MFMA bound, 4 x plain
+template <int AREG, bool TAU>
 __global__ __launch_bounds__(256) void xc_rho_kernel(int64_t npts, int nao, const double* __restrict__ ao,
                                                      const double* __restrict__ dao, const double* __restrict__ dm,
-                                                     double* __restrict__ rho, double* __restrict__ grad) {
+                                                     double* __restrict__ rho, double* __restrict__ grad,
+                                                     double* __restrict__ tau) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int KP = (nao + 3) & ~3, NT = (nao + 15) >> 4, NK = KP >> 2;
     double* ds0 = smem;             // [KP][16]  D_alpha[:, tile]
@@ -50,11 +61,11 @@ __global__ __launch_bounds__(256) void xc_rho_kernel(int64_t npts, int nao, cons
             afr[j] = (a_ok && k < nao) ? arow[k] : 0.0;
         }
     }
-    double pr[2][4], px[2][4], py[2][4], pz[2][4];
+    double pr[2][4], px[2][4], py[2][4], pz[2][4], pt[2][4];  // (pt: TAU only)
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pr[x][r] = px[x][r] = py[x][r] = pz[x][r] = 0.0;
+        for (int r = 0; r < 4; ++r) pr[x][r] = px[x][r] = py[x][r] = pz[x][r] = pt[x][r] = 0.0;
 
     for (int ct = 0; ct < NT; ++ct) {
         __syncthreads();  // the previous tile's fragments have been read
@@ -83,8 +94,13 @@ __global__ __launch_bounds__(256) void xc_rho_kernel(int64_t npts, int nao, cons
                 acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, ds1[k * 16 + fr], acc1, 0, 0, 0);
             }
         }
-        // epilogue: this tile of c against the same tile of ao / dao
+        // epilogue: this tile of c against the same tile of ao / dao; TAU: the dao values stay for the tau products
         const int m = 16 * ct + fr;
+        double dv[3][4];
+        if constexpr (TAU) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dv[0][r] = dv[1][r] = dv[2][r] = 0.0;
+        }
         if (m < nao) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -100,6 +116,25 @@ __global__ __launch_bounds__(256) void xc_rho_kernel(int64_t npts, int nao, cons
                     px[1][r] = fma(acc1[r], vx, px[1][r]);
                     py[1][r] = fma(acc1[r], vy, py[1][r]);
                     pz[1][r] = fma(acc1[r], vz, pz[1][r]);
+                    if constexpr (TAU) dv[0][r] = vx, dv[1][r] = vy, dv[2][r] = vz;
+                }
+            }
+        }
+        if constexpr (TAU) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double* drow = dao + a * plane + (a_ok ? ga : 0) * nao;
+                xc_v4 t0 = (xc_v4){0.0, 0.0, 0.0, 0.0}, t1 = (xc_v4){0.0, 0.0, 0.0, 0.0};
+                for (int j = 0; j < NK; ++j) {
+                    const int k = 4 * j + fk;
+                    const double d = (a_ok && k < nao) ? drow[k] : 0.0;
+                    t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(d, ds0[k * 16 + fr], t0, 0, 0, 0);
+                    t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(d, ds1[k * 16 + fr], t1, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {  // (dv = 0 outside the arrays)
+                    pt[0][r] = fma(t0[r], dv[a][r], pt[0][r]);
+                    pt[1][r] = fma(t1[r], dv[a][r], pt[1][r]);
                 }
             }
         }
@@ -109,13 +144,14 @@ __global__ __launch_bounds__(256) void xc_rho_kernel(int64_t npts, int nao, cons
     for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            double a = pr[x][r], b = px[x][r], c = py[x][r], d = pz[x][r];
+            double a = pr[x][r], b = px[x][r], c = py[x][r], d = pz[x][r], t = pt[x][r];
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) {
                 a += __shfl_xor(a, o, 64);
                 b += __shfl_xor(b, o, 64);
                 c += __shfl_xor(c, o, 64);
                 d += __shfl_xor(d, o, 64);
+                if constexpr (TAU) t += __shfl_xor(t, o, 64);
             }
             const int64_t g = gw + fk + 4 * r;
             if (fr == 0 && g < npts) {
@@ -123,6 +159,7 @@ __global__ __launch_bounds__(256) void xc_rho_kernel(int64_t npts, int nao, cons
                 grad[(3 * x + 0) * npts + g] = 2.0 * b;
                 grad[(3 * x + 1) * npts + g] = 2.0 * c;
                 grad[(3 * x + 2) * npts + g] = 2.0 * d;
+                if constexpr (TAU) tau[x * npts + g] = 0.5 * t;
             }
         }
 }
@@ -430,483 +467,6 @@ __device__ __forceinline__ void xc_pbe_c(double s, double ra, double rb, double 
     o.vbb += s * vs;
 }
 
-constexpr int XC_FN_THREADS = 256;
-
-// CODE: NBX_XC_SLATER / _LDA_VWN_RPA / _LDA_VWN5 / _B3LYP / _LDA_PW_MOD / _PBE / _PBEH / _BLYP / _B3LYP5, and the
-// range-separated NBX_XC_CAM_B3LYP / _LC_BLYP of nbx_xc_functional_rs, which alone read `omega` (the semi-local
-// part; the exact-exchange fractions are the caller's), one instantiation each: a kernel holding every branch would
-// charge the registers of PBE correlation to the LDA codes.  Conventions of nbed_amd.xc.XCProvider.__call__ (the torch
-// expression this kernel replaces): densities clamped from below at rho_floor / 2, sigma_aa and sigma_bb lifted by
-// 1e-40, points with rho_a + rho_b <= rho_floor dropped; outputs carry the quadrature weights:
-//   vr[x][g]     = w keep dE/drho_x
-//   vec[x][a][g] = w keep (2 dE/dsigma_xx grad rho_x + dE/dsigma_ab grad rho_other)[a]
-//   part[blk]    = (sum w keep e, sum w (rho_a + rho_b)) of the block
-template <int CODE>
-__global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_kernel(int64_t npts, const double* __restrict__ rho,
-                                                                      const double* __restrict__ grad,
-                                                                      const double* __restrict__ w, double rho_floor,
-                                                                      double omega, double* __restrict__ vr,
-                                                                      double* __restrict__ vec, double* __restrict__ part) {
-    __shared__ double red[17];
-    const int64_t g = (int64_t)blockIdx.x * XC_FN_THREADS + threadIdx.x;
-    double e_w = 0.0, n_w = 0.0;
-    if (g < npts) {
-        const double r0 = rho[g], r1 = rho[npts + g], wg = w[g];
-        const double gax = grad[g], gay = grad[npts + g], gaz = grad[2 * npts + g];
-        const double gbx = grad[3 * npts + g], gby = grad[4 * npts + g], gbz = grad[5 * npts + g];
-        n_w = wg * (r0 + r1);
-        const double keep = (r0 + r1) > rho_floor ? 1.0 : 0.0;
-        const double ra = fmax(r0, 0.5 * rho_floor), rb = fmax(r1, 0.5 * rho_floor);
-        const double saa = fma(gax, gax, fma(gay, gay, gaz * gaz)) + 1.0e-40;
-        const double sbb = fma(gbx, gbx, fma(gby, gby, gbz * gbz)) + 1.0e-40;
-        const double sab = fma(gax, gbx, fma(gay, gby, gaz * gbz));
-        XcDer o = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (CODE == NBX_XC_SLATER) {
-            xc_slater(1.0, ra, rb, o);
-        } else if (CODE == NBX_XC_LDA_VWN_RPA) {
-            xc_slater(1.0, ra, rb, o);
-            xc_vwn<true>(1.0, ra, rb, o);
-        } else if (CODE == NBX_XC_LDA_VWN5) {
-            xc_slater(1.0, ra, rb, o);
-            xc_vwn<false>(1.0, ra, rb, o);
-        } else if (CODE == NBX_XC_B3LYP || CODE == NBX_XC_B3LYP5) {
-            xc_slater(0.8, ra, rb, o);
-            xc_b88(0.72, ra, saa, o.e, o.va, o.vaa);
-            xc_b88(0.72, rb, sbb, o.e, o.vb, o.vbb);
-            xc_vwn<CODE == NBX_XC_B3LYP>(0.19, ra, rb, o);
-            xc_lyp(0.81, ra, rb, saa, sab, sbb, o);
-        } else if (CODE == NBX_XC_LDA_PW_MOD) {
-            xc_slater(1.0, ra, rb, o);
-            xc_pw_mod(1.0, ra, rb, o);
-        } else if (CODE == NBX_XC_PBE || CODE == NBX_XC_PBEH) {
-            const double ax = CODE == NBX_XC_PBE ? 1.0 : 0.75;
-            xc_pbe_x(ax, ra, saa, o.e, o.va, o.vaa);
-            xc_pbe_x(ax, rb, sbb, o.e, o.vb, o.vbb);
-            xc_pbe_c(1.0, ra, rb, saa, sab, sbb, o);
-        } else if (CODE == NBX_XC_CAM_B3LYP) {  // (1 - 0.19 - 0.46) B88 + 0.46 B88^sr(omega) + 0.81 LYP + 0.19 VWN5
-            xc_slater(0.35, ra, rb, o);
-            xc_b88(0.35, ra, saa, o.e, o.va, o.vaa);
-            xc_b88(0.35, rb, sbb, o.e, o.vb, o.vbb);
-            xc_b88_sr(0.46, omega, ra, saa, o.e, o.va, o.vaa);
-            xc_b88_sr(0.46, omega, rb, sbb, o.e, o.vb, o.vbb);
-            xc_vwn<false>(0.19, ra, rb, o);
-            xc_lyp(0.81, ra, rb, saa, sab, sbb, o);
-        } else if (CODE == NBX_XC_LC_BLYP) {  // B88^sr(omega) + LYP
-            xc_b88_sr(1.0, omega, ra, saa, o.e, o.va, o.vaa);
-            xc_b88_sr(1.0, omega, rb, sbb, o.e, o.vb, o.vbb);
-            xc_lyp(1.0, ra, rb, saa, sab, sbb, o);
-        } else {  // BLYP
-            xc_slater(1.0, ra, rb, o);
-            xc_b88(1.0, ra, saa, o.e, o.va, o.vaa);
-            xc_b88(1.0, rb, sbb, o.e, o.vb, o.vbb);
-            xc_lyp(1.0, ra, rb, saa, sab, sbb, o);
-        }
-        const double wk = wg * keep;
-        e_w = wk * o.e;
-        vr[g] = wk * o.va;
-        vr[npts + g] = wk * o.vb;
-        const double a2 = 2.0 * wk * o.vaa, b2 = 2.0 * wk * o.vbb, ab = wk * o.vab;
-        vec[g] = fma(a2, gax, ab * gbx);
-        vec[npts + g] = fma(a2, gay, ab * gby);
-        vec[2 * npts + g] = fma(a2, gaz, ab * gbz);
-        vec[3 * npts + g] = fma(b2, gbx, ab * gax);
-        vec[4 * npts + g] = fma(b2, gby, ab * gay);
-        vec[5 * npts + g] = fma(b2, gbz, ab * gaz);
-    }
-    const double es = nbx_block_sum(e_w, red);
-    const double ns = nbx_block_sum(n_w, red);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = es;
-        part[2 * blockIdx.x + 1] = ns;
-    }
-}
-
-// sums the block partials in a fixed order (one workgroup): out[0] = E_xc, out[1] = integrated electron count
-__global__ __launch_bounds__(256) void xc_sums_kernel(int nblk, const double* __restrict__ part, double* __restrict__ out) {
-    __shared__ double red[17];
-    double e = 0.0, n = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-        e += part[2 * i];
-        n += part[2 * i + 1];
-    }
-    e = nbx_block_sum(e, red);
-    n = nbx_block_sum(n, red);
-    if (threadIdx.x == 0) {
-        out[0] = e;
-        out[1] = n;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ potential pass
-// Workgroup = BT waves; block (bm, bn) of the (nao x nao) result, 16 BT rows and columns; wave w owns tile row w of
-// the block and all BT column tiles.  Grid points are consumed 16 at a time: the threads build the 16 x (16 BT)
-// tile of `half` into LDS (double buffered: one barrier per step), every wave multiplies its ao^T fragments (read
-// straight from global memory: 16 consecutive AO columns per grid point) with it.
-template <int BT>
-__global__ __launch_bounds__(64 * BT) void xc_vmat_kernel(int64_t npts, int nao, int64_t chunk, int nblk,
-                                                          const double* __restrict__ ao, const double* __restrict__ dao,
-                                                          const double* __restrict__ vr, const double* __restrict__ vec,
-                                                          double* __restrict__ part) {
-    constexpr int W = 16 * BT, LD = (W % 32 == 16) ? W : W + 16, NT = 64 * BT;
-    __shared__ __attribute__((aligned(16))) double hs[2][16 * LD];
-    const int x = blockIdx.z;
-    const int bm = blockIdx.y / nblk, bn = blockIdx.y - bm * nblk;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fk = lane >> 4;
-    const int64_t g_begin = (int64_t)blockIdx.x * chunk, g_end = min(npts, g_begin + chunk);
-    const int64_t plane = npts * (int64_t)nao;
-    const double* vrx = vr + (int64_t)x * npts;
-    const double* vcx = vec + (int64_t)(3 * x) * npts;
-    const int m = W * bm + 16 * wave + fr;  // the A-fragment column of ao (row of the result) of this lane
-    const bool m_ok = m < nao;
-    xc_v4 acc[BT];
-#pragma unroll
-    for (int c = 0; c < BT; ++c) acc[c] = (xc_v4){0.0, 0.0, 0.0, 0.0};
-
-    auto produce = [&](int buf, int64_t g0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {  // 16 W elements over NT = 4 W threads
-            const int e = threadIdx.x + i * NT;
-            const int gl = e / W, nl = e - gl * W;
-            const int64_t g = g0 + gl;
-            const int n = W * bn + nl;
-            double h = 0.0;
-            if (g < g_end && n < nao) {
-                const int64_t off = g * nao + n;
-                h = fma(0.5 * vrx[g], ao[off],
-                        fma(vcx[g], dao[off], fma(vcx[npts + g], dao[plane + off], vcx[2 * npts + g] * dao[2 * plane + off])));
-            }
-            hs[buf][gl * LD + nl] = h;
-        }
-    };
-
-    int buf = 0;
-    if (g_begin < g_end) produce(0, g_begin);
-    for (int64_t g0 = g_begin; g0 < g_end; g0 += 16) {
-        __syncthreads();  // hs[buf] is complete; hs[buf ^ 1] has been consumed
-        if (g0 + 16 < g_end) produce(buf ^ 1, g0 + 16);
-        double a[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int64_t g = g0 + 4 * kk + fk;
-            a[kk] = (m_ok && g < g_end) ? ao[g * nao + m] : 0.0;
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int c = 0; c < BT; ++c)
-                acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], hs[buf][(4 * kk + fk) * LD + 16 * c + fr], acc[c], 0, 0, 0);
-        buf ^= 1;
-    }
-    // this chunk's contribution to the block: part[chunk][x][row][col]
-    double* out = part + ((int64_t)blockIdx.x * 2 + x) * (int64_t)nao * nao;
-#pragma unroll
-    for (int c = 0; c < BT; ++c) {
-        const int col = W * bn + 16 * c + fr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = W * bm + 16 * wave + fk + 4 * r;
-            if (row < nao && col < nao) out[(int64_t)row * nao + col] = acc[c][r];
-        }
-    }
-}
-
-// v[x][m][n] = sum_chunks (part[c][x][m][n] + part[c][x][n][m]), chunks in ascending order
-__global__ __launch_bounds__(256) void xc_vmat_reduce_kernel(int nao, int nchunk, const double* __restrict__ part,
-                                                             double* __restrict__ v) {
-    const int64_t n2 = (int64_t)nao * nao;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= 2 * n2) return;
-    const int x = (int)(i / n2);
-    const int64_t e = i - x * n2;
-    const int m = (int)(e / nao), n = (int)(e - (int64_t)m * nao);
-    const int64_t et = (int64_t)n * nao + m;
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) {
-        const double* p = part + ((int64_t)c * 2 + x) * n2;
-        s += p[e] + p[et];
-    }
-    v[i] = s;
-}
-
-int vmat_bt(int64_t nao) {  // tiles per block side: the least padded 16 BT grid over nao, the larger BT on a tie
-    int best = 1;
-    int64_t best_pad = -1;
-    for (int bt = 1; bt <= 5; ++bt) {
-        const int64_t w = 16 * bt, pad = nbx_cdiv(nao, w) * w;
-        if (best_pad < 0 || pad <= best_pad) {
-            best = bt;
-            best_pad = pad;
-        }
-    }
-    return best;
-}
-
-int64_t vmat_chunk(int64_t npts, int64_t nao) {  // grid points per workgroup: enough workgroups to fill the chip
-    const int bt = vmat_bt(nao);
-    const int64_t nblk = nbx_cdiv(nao, 16 * bt);
-    int64_t chunk = 2048;
-    while (chunk > 256 && nbx_cdiv(npts, chunk) * nblk * nblk * 2 < 1024) chunk >>= 1;
-    return chunk;
-}
-
-size_t xc_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-}  // namespace
-
-extern "C" int nbx_xc_rho(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
-                          const double* d_dm, double* d_rho, double* d_grad) {
-    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_dm && d_rho && d_grad && npts >= 0 && nao >= 1);
-    const int64_t kp = (nao + 3) & ~3ll;
-    const size_t lds = (size_t)(2 * kp * 16) * sizeof(double);
-    if (lds > 160 * 1024) {
-        nbx_set_error("nbx_xc_rho: nao = %lld beyond the LDS-resident density slab (limit 640)", (long long)nao);
-        return NBX_E_UNSUPPORTED;
-    }
-    if (npts == 0) return NBX_OK;
-    const dim3 grid((unsigned)nbx_cdiv(npts, 64));
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xc_rho_kernel<40>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xc_rho_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr_set = true;
-    }
-    if (kp <= 160)
-        hipLaunchKernelGGL(xc_rho_kernel<40>, grid, dim3(256), lds, ctx->stream, npts, (int)nao, d_ao, d_dao, d_dm, d_rho, d_grad);
-    else
-        hipLaunchKernelGGL(xc_rho_kernel<0>, grid, dim3(256), lds, ctx->stream, npts, (int)nao, d_ao, d_dao, d_dm, d_rho, d_grad);
-    NBX_LAUNCH_CHECK();
-    return NBX_OK;
-}
-
-extern "C" size_t nbx_xc_functional_worksize(int64_t npts) {
-    return npts <= 0 ? 256 : xc_align256((size_t)(2 * nbx_cdiv(npts, XC_FN_THREADS)) * sizeof(double));
-}
-
-namespace {
-
-// nbx_xc_functional (codes 0 .. 8, omega unused) and nbx_xc_functional_rs (codes from 16 on), arguments checked
-int xc_functional_launch(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho, const double* d_grad,
-                         const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
-                         size_t work_bytes) {
-    NBX_CHECK_ARG(ctx && d_rho && d_grad && d_w && d_vr && d_vec && d_sums && d_work && npts >= 0);
-    NBX_CHECK_ARG(rho_floor > 0.0 && work_bytes >= nbx_xc_functional_worksize(npts));
-    if (npts == 0) return nbx_memset(ctx, d_sums, 0, 2 * sizeof(double));
-    const int64_t nblk = nbx_cdiv(npts, XC_FN_THREADS);
-    NBX_CHECK_ARG(nblk < (1ll << 30));
-    double* part = static_cast<double*>(d_work);
-#define NBX_XC_FN(CODE_)                                                                                                  \
-    case CODE_:                                                                                                           \
-        hipLaunchKernelGGL(xc_functional_kernel<CODE_>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,  \
-                           d_rho, d_grad, d_w, rho_floor, omega, d_vr, d_vec, part);                                      \
-        break
-    switch (code) {
-        NBX_XC_FN(NBX_XC_SLATER);
-        NBX_XC_FN(NBX_XC_LDA_VWN_RPA);
-        NBX_XC_FN(NBX_XC_LDA_VWN5);
-        NBX_XC_FN(NBX_XC_B3LYP);
-        NBX_XC_FN(NBX_XC_LDA_PW_MOD);
-        NBX_XC_FN(NBX_XC_PBE);
-        NBX_XC_FN(NBX_XC_PBEH);
-        NBX_XC_FN(NBX_XC_BLYP);
-        NBX_XC_FN(NBX_XC_B3LYP5);
-        NBX_XC_FN(NBX_XC_CAM_B3LYP);
-        default: NBX_XC_FN(NBX_XC_LC_BLYP);
-    }
-#undef NBX_XC_FN
-    NBX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(xc_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, (int)nblk, part, d_sums);
-    NBX_LAUNCH_CHECK();
-    return NBX_OK;
-}
-
-}  // namespace
-
-extern "C" int nbx_xc_functional(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
-                                 const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
-                                 size_t work_bytes) {
-    NBX_CHECK_ARG(code >= NBX_XC_SLATER && code <= NBX_XC_B3LYP5);
-    return xc_functional_launch(ctx, code, 0.0, npts, d_rho, d_grad, d_w, rho_floor, d_vr, d_vec, d_sums, d_work, work_bytes);
-}
-
-extern "C" int nbx_xc_functional_rs(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho,
-                                    const double* d_grad, const double* d_w, double rho_floor, double* d_vr, double* d_vec,
-                                    double* d_sums, void* d_work, size_t work_bytes) {
-    NBX_CHECK_ARG(code == NBX_XC_CAM_B3LYP || code == NBX_XC_LC_BLYP);
-    NBX_CHECK_ARG(omega >= 0.0 && omega < 1.0e150);  // (finite; 0 is the plain B88: F(0) = 1)
-    return xc_functional_launch(ctx, code, omega, npts, d_rho, d_grad, d_w, rho_floor, d_vr, d_vec, d_sums, d_work, work_bytes);
-}
-
-extern "C" size_t nbx_xc_vmat_worksize(int64_t npts, int64_t nao) {
-    if (npts <= 0 || nao <= 0) return 256;
-    const int64_t nchunk = nbx_cdiv(npts, vmat_chunk(npts, nao));
-    return xc_align256((size_t)(nchunk * 2 * nao * nao) * sizeof(double));
-}
-
-extern "C" int nbx_xc_vmat(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
-                           const double* d_vr, const double* d_vec, double* d_vxc, void* d_work, size_t work_bytes) {
-    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_vr && d_vec && d_vxc && npts >= 0 && nao >= 1 && nao <= (1 << 15));
-    const int64_t n2 = nao * nao;
-    if (npts == 0) return nbx_memset(ctx, d_vxc, 0, (size_t)(2 * n2) * sizeof(double));
-    NBX_CHECK_ARG(d_work && work_bytes >= nbx_xc_vmat_worksize(npts, nao));
-    const int bt = vmat_bt(nao);
-    const int64_t chunk = vmat_chunk(npts, nao), nchunk = nbx_cdiv(npts, chunk), nblk = nbx_cdiv(nao, 16 * bt);
-    NBX_CHECK_ARG(nblk * nblk <= 65535 && nchunk < (1ll << 31));
-    double* part = static_cast<double*>(d_work);
-    const dim3 grid((unsigned)nchunk, (unsigned)(nblk * nblk), 2);
-#define NBX_VMAT(BT_)                                                                                                       \
-    hipLaunchKernelGGL(xc_vmat_kernel<BT_>, grid, dim3(64 * BT_), 0, ctx->stream, npts, (int)nao, chunk, (int)nblk, d_ao, d_dao, \
-                       d_vr, d_vec, part)
-    switch (bt) {
-        case 1: NBX_VMAT(1); break;
-        case 2: NBX_VMAT(2); break;
-        case 3: NBX_VMAT(3); break;
-        case 4: NBX_VMAT(4); break;
-        default: NBX_VMAT(5); break;
-    }
-#undef NBX_VMAT
-    NBX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(xc_vmat_reduce_kernel, dim3((unsigned)nbx_cdiv(2 * n2, 256)), dim3(256), 0, ctx->stream, (int)nao,
-                       (int)nchunk, part, d_vxc);
-    NBX_LAUNCH_CHECK();
-    return NBX_OK;
-}
-
-// =============================================================================================== meta-GGAs
-// The same three passes with the kinetic-energy density tau_x = 1/2 sum_i |grad psi_i|^2 carried through them
-// (nbx_xc_rho_tau, nbx_xc_functional_mgga, nbx_xc_vmat_tau); the kernels above are untouched.
-namespace {
-
-// ------------------------------------------------------------------------------------------------ density pass with tau
-// xc_rho_kernel with three more products per column tile: after c = ao D (same fragments, same order, same epilogue:
-// rho and grad rho come out bit for bit) the slab of D that is already in LDS is multiplied by the fragments of dao_x,
-// dao_y and dao_z in turn (streamed: 3 x 40 doubles would not fit beside the ao fragments), and each product is reduced
-// against the dao_a values the epilogue of rho has just read: tau = 1/2 sum_a sum_m (dao_a D)[g][m] dao_a[g][m].
-// The passes are sequential inside the tile loop: two accumulators live at a time.           -- MFMA bound, 4 x xc_rho
-template <int AREG>
-__global__ __launch_bounds__(256) void xc_rho_tau_kernel(int64_t npts, int nao, const double* __restrict__ ao,
-                                                         const double* __restrict__ dao, const double* __restrict__ dm,
-                                                         double* __restrict__ rho, double* __restrict__ grad,
-                                                         double* __restrict__ tau) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int KP = (nao + 3) & ~3, NT = (nao + 15) >> 4, NK = KP >> 2;
-    double* ds0 = smem;             // [KP][16]  D_alpha[:, tile]
-    double* ds1 = smem + KP * 16;   // [KP][16]  D_beta
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fk = lane >> 4;
-    const int64_t gw = (int64_t)blockIdx.x * 64 + wave * 16;
-    const int64_t plane = npts * (int64_t)nao, n2 = (int64_t)nao * nao;
-    const int64_t ga = gw + fr;  // the A-fragment row of this lane
-    const bool a_ok = ga < npts;
-    const double* arow = ao + (a_ok ? ga : 0) * nao;
-    double afr[AREG > 0 ? AREG : 1];
-    if (AREG > 0) {
-#pragma unroll
-        for (int j = 0; j < AREG; ++j) {
-            const int k = 4 * j + fk;
-            afr[j] = (a_ok && k < nao) ? arow[k] : 0.0;
-        }
-    }
-    double pr[2][4], px[2][4], py[2][4], pz[2][4], pt[2][4];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pr[x][r] = px[x][r] = py[x][r] = pz[x][r] = pt[x][r] = 0.0;
-
-    for (int ct = 0; ct < NT; ++ct) {
-        __syncthreads();  // the previous tile's fragments have been read
-        for (int e = threadIdx.x; e < KP * 16; e += 256) {
-            const int k = e >> 4, c = 16 * ct + (e & 15);
-            const bool in = k < nao && c < nao;
-            ds0[e] = in ? dm[(int64_t)k * nao + c] : 0.0;
-            ds1[e] = in ? dm[n2 + (int64_t)k * nao + c] : 0.0;
-        }
-        __syncthreads();
-        xc_v4 acc0 = (xc_v4){0.0, 0.0, 0.0, 0.0}, acc1 = (xc_v4){0.0, 0.0, 0.0, 0.0};
-        if (AREG > 0) {
-#pragma unroll
-            for (int j = 0; j < AREG; ++j) {
-                if (j < NK) {
-                    const int k = 4 * j + fk;
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[j], ds0[k * 16 + fr], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[j], ds1[k * 16 + fr], acc1, 0, 0, 0);
-                }
-            }
-        } else {
-            for (int j = 0; j < NK; ++j) {
-                const int k = 4 * j + fk;
-                const double a = (a_ok && k < nao) ? arow[k] : 0.0;
-                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, ds0[k * 16 + fr], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, ds1[k * 16 + fr], acc1, 0, 0, 0);
-            }
-        }
-        // epilogue: this tile of c against the same tile of ao / dao; the dao values stay for the tau products
-        const int m = 16 * ct + fr;
-        double dv[3][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dv[0][r] = dv[1][r] = dv[2][r] = 0.0;
-        if (m < nao) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t g = gw + fk + 4 * r;
-                if (g < npts) {
-                    const int64_t off = g * nao + m;
-                    const double v0 = ao[off], vx = dao[off], vy = dao[plane + off], vz = dao[2 * plane + off];
-                    pr[0][r] = fma(acc0[r], v0, pr[0][r]);
-                    px[0][r] = fma(acc0[r], vx, px[0][r]);
-                    py[0][r] = fma(acc0[r], vy, py[0][r]);
-                    pz[0][r] = fma(acc0[r], vz, pz[0][r]);
-                    pr[1][r] = fma(acc1[r], v0, pr[1][r]);
-                    px[1][r] = fma(acc1[r], vx, px[1][r]);
-                    py[1][r] = fma(acc1[r], vy, py[1][r]);
-                    pz[1][r] = fma(acc1[r], vz, pz[1][r]);
-                    dv[0][r] = vx, dv[1][r] = vy, dv[2][r] = vz;
-                }
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double* drow = dao + a * plane + (a_ok ? ga : 0) * nao;
-            xc_v4 t0 = (xc_v4){0.0, 0.0, 0.0, 0.0}, t1 = (xc_v4){0.0, 0.0, 0.0, 0.0};
-            for (int j = 0; j < NK; ++j) {
-                const int k = 4 * j + fk;
-                const double d = (a_ok && k < nao) ? drow[k] : 0.0;
-                t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(d, ds0[k * 16 + fr], t0, 0, 0, 0);
-                t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(d, ds1[k * 16 + fr], t1, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {  // (dv = 0 outside the arrays)
-                pt[0][r] = fma(t0[r], dv[a][r], pt[0][r]);
-                pt[1][r] = fma(t1[r], dv[a][r], pt[1][r]);
-            }
-        }
-    }
-    // sum over the 16 lanes (columns) that share the rows fk + 4 r: xor shuffles stay inside the 16-lane group
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            double a = pr[x][r], b = px[x][r], c = py[x][r], d = pz[x][r], t = pt[x][r];
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) {
-                a += __shfl_xor(a, o, 64);
-                b += __shfl_xor(b, o, 64);
-                c += __shfl_xor(c, o, 64);
-                d += __shfl_xor(d, o, 64);
-                t += __shfl_xor(t, o, 64);
-            }
-            const int64_t g = gw + fk + 4 * r;
-            if (fr == 0 && g < npts) {
-                rho[x * npts + g] = a;
-                grad[(3 * x + 0) * npts + g] = 2.0 * b;
-                grad[(3 * x + 1) * npts + g] = 2.0 * c;
-                grad[(3 * x + 2) * npts + g] = 2.0 * d;
-                tau[x * npts + g] = 0.5 * t;
-            }
-        }
-}
-
-// ------------------------------------------------------------------------------------------------ TPSS
 // Conventions (nbed_amd.xc, "Meta-GGA conventions"): wherever z = tau_W / tau is formed, tau is clamped from below at
 // tau_W = sigma / (8 n) of the same clamped quantities by the test tau >= sigma / (8 n) * XC_TPSS_CLAMP; where it fails
 // z = 1 and alpha = 0 are constants.  XC_TPSS_CLAMP = 1 - 1e-10: a one-orbital density has tau = tau_W at every point up
@@ -1077,22 +637,36 @@ __device__ __forceinline__ void xc_tpss_c(double ra, double rb, double saa, doub
     e = n * eps;
 }
 
-// nbx_xc_functional's kernel for the meta-GGAs: CODE = NBX_XC_TPSS / NBX_XC_TPSSH (0.9 of the exchange; the 0.1 of exact
-// exchange is the caller's).  Inputs, conventions and outputs of xc_functional_kernel, plus tau (2, npts) in and
-//   vt[x][g] = w keep dE/dtau_x
-// out.  The exchange clamps each channel's tau against its own tau_W, the correlation tau_a + tau_b against the total's.
+constexpr int XC_FN_THREADS = 256;
+
+// CODE: NBX_XC_SLATER / _LDA_VWN_RPA / _LDA_VWN5 / _B3LYP / _LDA_PW_MOD / _PBE / _PBEH / _BLYP / _B3LYP5, the
+// range-separated NBX_XC_CAM_B3LYP / _LC_BLYP of nbx_xc_functional_rs, which alone read `omega` (the semi-local
+// part; the exact-exchange fractions are the caller's), and the meta-GGAs NBX_XC_TPSS / _TPSSH (0.9 of the exchange;
+// the 0.1 of exact exchange is the caller's) of nbx_xc_functional_mgga, which alone read `tau` (2, npts) and write `vt`
+// (both null otherwise, and last, so that the other codes find their arguments where they were without them);
+// one instantiation each: a kernel holding every branch would charge the registers of the heaviest code to all of them
+// (the meta-GGAs take all 256 VGPRs, the LDA codes 52).  Conventions of nbed_amd.xc.XCProvider.__call__ (the torch
+// expression this kernel replaces): densities clamped from below at rho_floor / 2, sigma_aa and sigma_bb lifted by
+// 1e-40, points with rho_a + rho_b <= rho_floor dropped; the TPSS exchange clamps each channel's tau against its own
+// tau_W, the correlation tau_a + tau_b against the total's; outputs carry the quadrature weights:
+//   vr[x][g]     = w keep dE/drho_x
+//   vec[x][a][g] = w keep (2 dE/dsigma_xx grad rho_x + dE/dsigma_ab grad rho_other)[a]
+//   vt[x][g]     = w keep dE/dtau_x                                                        (meta-GGAs)
+//   part[blk]    = (sum w keep e, sum w (rho_a + rho_b)) of the block
 template <int CODE>
-__global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_mgga_kernel(int64_t npts, const double* __restrict__ rho,
-                                                                           const double* __restrict__ grad,
-                                                                           const double* __restrict__ tau,
-                                                                           const double* __restrict__ w, double rho_floor,
-                                                                           double* __restrict__ vr, double* __restrict__ vec,
-                                                                           double* __restrict__ vt, double* __restrict__ part) {
+__global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_kernel(int64_t npts, const double* __restrict__ rho,
+                                                                      const double* __restrict__ grad,
+                                                                      const double* __restrict__ w, double rho_floor,
+                                                                      double omega, double* __restrict__ vr,
+                                                                      double* __restrict__ vec, double* __restrict__ part,
+                                                                      const double* __restrict__ tau,
+                                                                      double* __restrict__ vt) {
+    constexpr bool MGGA = CODE == NBX_XC_TPSS || CODE == NBX_XC_TPSSH;
     __shared__ double red[17];
     const int64_t g = (int64_t)blockIdx.x * XC_FN_THREADS + threadIdx.x;
     double e_w = 0.0, n_w = 0.0;
     if (g < npts) {
-        const double r0 = rho[g], r1 = rho[npts + g], wg = w[g], ta = tau[g], tb = tau[npts + g];
+        const double r0 = rho[g], r1 = rho[npts + g], wg = w[g];
         const double gax = grad[g], gay = grad[npts + g], gaz = grad[2 * npts + g];
         const double gbx = grad[3 * npts + g], gby = grad[4 * npts + g], gbz = grad[5 * npts + g];
         n_w = wg * (r0 + r1);
@@ -1101,21 +675,64 @@ __global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_mgga_kernel(int64
         const double saa = fma(gax, gax, fma(gay, gay, gaz * gaz)) + 1.0e-40;
         const double sbb = fma(gbx, gbx, fma(gby, gby, gbz * gbz)) + 1.0e-40;
         const double sab = fma(gax, gbx, fma(gay, gby, gaz * gbz));
-        const double ax = CODE == NBX_XC_TPSS ? 1.0 : 0.9;
         XcDer o = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        double vta = 0.0, vtb = 0.0;
-        xc_tpss_x(ax, ra, saa, ta, o.e, o.va, o.vaa, vta);
-        xc_tpss_x(ax, rb, sbb, tb, o.e, o.vb, o.vbb, vtb);
-        double ec, dc[6];
-        xc_tpss_c(ra, rb, saa, sab, sbb, ta + tb, ec, dc);
-        o.e += ec, o.va += dc[0], o.vb += dc[1], o.vaa += dc[2], o.vab += dc[3], o.vbb += dc[4];
-        vta += dc[5], vtb += dc[5];
+        double vta = 0.0, vtb = 0.0;  // dE/dtau_x (meta-GGAs)
+        if constexpr (MGGA) {
+            const double ax = CODE == NBX_XC_TPSS ? 1.0 : 0.9, ta = tau[g], tb = tau[npts + g];
+            xc_tpss_x(ax, ra, saa, ta, o.e, o.va, o.vaa, vta);
+            xc_tpss_x(ax, rb, sbb, tb, o.e, o.vb, o.vbb, vtb);
+            double ec, dc[6];
+            xc_tpss_c(ra, rb, saa, sab, sbb, ta + tb, ec, dc);
+            o.e += ec, o.va += dc[0], o.vb += dc[1], o.vaa += dc[2], o.vab += dc[3], o.vbb += dc[4];
+            vta += dc[5], vtb += dc[5];
+        } else if (CODE == NBX_XC_SLATER) {
+            xc_slater(1.0, ra, rb, o);
+        } else if (CODE == NBX_XC_LDA_VWN_RPA) {
+            xc_slater(1.0, ra, rb, o);
+            xc_vwn<true>(1.0, ra, rb, o);
+        } else if (CODE == NBX_XC_LDA_VWN5) {
+            xc_slater(1.0, ra, rb, o);
+            xc_vwn<false>(1.0, ra, rb, o);
+        } else if (CODE == NBX_XC_B3LYP || CODE == NBX_XC_B3LYP5) {
+            xc_slater(0.8, ra, rb, o);
+            xc_b88(0.72, ra, saa, o.e, o.va, o.vaa);
+            xc_b88(0.72, rb, sbb, o.e, o.vb, o.vbb);
+            xc_vwn<CODE == NBX_XC_B3LYP>(0.19, ra, rb, o);
+            xc_lyp(0.81, ra, rb, saa, sab, sbb, o);
+        } else if (CODE == NBX_XC_LDA_PW_MOD) {
+            xc_slater(1.0, ra, rb, o);
+            xc_pw_mod(1.0, ra, rb, o);
+        } else if (CODE == NBX_XC_PBE || CODE == NBX_XC_PBEH) {
+            const double ax = CODE == NBX_XC_PBE ? 1.0 : 0.75;
+            xc_pbe_x(ax, ra, saa, o.e, o.va, o.vaa);
+            xc_pbe_x(ax, rb, sbb, o.e, o.vb, o.vbb);
+            xc_pbe_c(1.0, ra, rb, saa, sab, sbb, o);
+        } else if (CODE == NBX_XC_CAM_B3LYP) {  // (1 - 0.19 - 0.46) B88 + 0.46 B88^sr(omega) + 0.81 LYP + 0.19 VWN5
+            xc_slater(0.35, ra, rb, o);
+            xc_b88(0.35, ra, saa, o.e, o.va, o.vaa);
+            xc_b88(0.35, rb, sbb, o.e, o.vb, o.vbb);
+            xc_b88_sr(0.46, omega, ra, saa, o.e, o.va, o.vaa);
+            xc_b88_sr(0.46, omega, rb, sbb, o.e, o.vb, o.vbb);
+            xc_vwn<false>(0.19, ra, rb, o);
+            xc_lyp(0.81, ra, rb, saa, sab, sbb, o);
+        } else if (CODE == NBX_XC_LC_BLYP) {  // B88^sr(omega) + LYP
+            xc_b88_sr(1.0, omega, ra, saa, o.e, o.va, o.vaa);
+            xc_b88_sr(1.0, omega, rb, sbb, o.e, o.vb, o.vbb);
+            xc_lyp(1.0, ra, rb, saa, sab, sbb, o);
+        } else {  // BLYP
+            xc_slater(1.0, ra, rb, o);
+            xc_b88(1.0, ra, saa, o.e, o.va, o.vaa);
+            xc_b88(1.0, rb, sbb, o.e, o.vb, o.vbb);
+            xc_lyp(1.0, ra, rb, saa, sab, sbb, o);
+        }
         const double wk = wg * keep;
         e_w = wk * o.e;
         vr[g] = wk * o.va;
         vr[npts + g] = wk * o.vb;
-        vt[g] = wk * vta;
-        vt[npts + g] = wk * vtb;
+        if constexpr (MGGA) {
+            vt[g] = wk * vta;
+            vt[npts + g] = wk * vtb;
+        }
         const double a2 = 2.0 * wk * o.vaa, b2 = 2.0 * wk * o.vbb, ab = wk * o.vab;
         vec[g] = fma(a2, gax, ab * gbx);
         vec[npts + g] = fma(a2, gay, ab * gby);
@@ -1132,16 +749,37 @@ __global__ __launch_bounds__(XC_FN_THREADS) void xc_functional_mgga_kernel(int64
     }
 }
 
-// ------------------------------------------------------------------------------------------------ potential pass with tau
-// xc_vmat_kernel with four products per step of 16 grid points, all into the same accumulators: A = ao against
-// B = half (xc_vmat_kernel's step, unchanged), then A = dao_a against B = 1/4 vt dao_a for a = x, y, z, each B built on
-// the fly.  The (step, operand) pairs run through the same double-buffered LDS tile as one sequence four times as long:
-// no more LDS, one barrier per product.  With vt = 0 the three extra products add zeros: xc_vmat_kernel's bits.
-template <int BT>
-__global__ __launch_bounds__(64 * BT) void xc_vmat_tau_kernel(int64_t npts, int nao, int64_t chunk, int nblk,
-                                                              const double* __restrict__ ao, const double* __restrict__ dao,
-                                                              const double* __restrict__ vr, const double* __restrict__ vec,
-                                                              const double* __restrict__ vt, double* __restrict__ part) {
+// sums the block partials in a fixed order (one workgroup): out[0] = E_xc, out[1] = integrated electron count
+__global__ __launch_bounds__(256) void xc_sums_kernel(int nblk, const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double red[17];
+    double e = 0.0, n = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) {
+        e += part[2 * i];
+        n += part[2 * i + 1];
+    }
+    e = nbx_block_sum(e, red);
+    n = nbx_block_sum(n, red);
+    if (threadIdx.x == 0) {
+        out[0] = e;
+        out[1] = n;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ potential pass
+// Workgroup = BT waves; block (bm, bn) of the (nao x nao) result, 16 BT rows and columns; wave w owns tile row w of
+// the block and all BT column tiles.  Grid points are consumed 16 at a time: the threads build the 16 x (16 BT)
+// tile of `half` into LDS (double buffered: one barrier per step), every wave multiplies its ao^T fragments (read
+// straight from global memory: 16 consecutive AO columns per grid point) with it.
+// TAU (`vt` is read by no other instantiation; null there): four products per step of 16 grid points, all into the same
+// accumulators: operand 0 is the plain step, A = ao against B = half; operands 1 .. 3 are A = dao_a against
+// B = 1/4 vt dao_a for a = x, y, z, each B built on the fly.  The (step, operand) pairs run through the same
+// double-buffered LDS tile as one sequence four times as long: no more LDS, one barrier per product.  With vt = 0 the
+// three extra products add zeros: the plain kernel's bits.
+template <int BT, bool TAU>
+__global__ __launch_bounds__(64 * BT) void xc_vmat_kernel(int64_t npts, int nao, int64_t chunk, int nblk,
+                                                          const double* __restrict__ ao, const double* __restrict__ dao,
+                                                          const double* __restrict__ vr, const double* __restrict__ vec,
+                                                          double* __restrict__ part, const double* __restrict__ vt) {
     constexpr int W = 16 * BT, LD = (W % 32 == 16) ? W : W + 16, NT = 64 * BT;
     __shared__ __attribute__((aligned(16))) double hs[2][16 * LD];
     const int x = blockIdx.z;
@@ -1151,14 +789,14 @@ __global__ __launch_bounds__(64 * BT) void xc_vmat_tau_kernel(int64_t npts, int 
     const int64_t plane = npts * (int64_t)nao;
     const double* vrx = vr + (int64_t)x * npts;
     const double* vcx = vec + (int64_t)(3 * x) * npts;
-    const double* vtx = vt + (int64_t)x * npts;
+    const double* vtx = TAU ? vt + (int64_t)x * npts : nullptr;
     const int m = W * bm + 16 * wave + fr;  // the A-fragment column of ao / dao_a (row of the result) of this lane
     const bool m_ok = m < nao;
     xc_v4 acc[BT];
 #pragma unroll
     for (int c = 0; c < BT; ++c) acc[c] = (xc_v4){0.0, 0.0, 0.0, 0.0};
 
-    auto produce = [&](int buf, int64_t g0, int op) {
+    auto produce = [&](int buf, int64_t g0, int op) {  // the B tile of operand `op` at the 16 points from g0 on
 #pragma unroll
         for (int i = 0; i < 4; ++i) {  // 16 W elements over NT = 4 W threads
             const int e = threadIdx.x + i * NT;
@@ -1168,7 +806,7 @@ __global__ __launch_bounds__(64 * BT) void xc_vmat_tau_kernel(int64_t npts, int 
             double h = 0.0;
             if (g < g_end && n < nao) {
                 const int64_t off = g * nao + n;
-                if (op == 0)
+                if (!TAU || op == 0)
                     h = fma(0.5 * vrx[g], ao[off],
                             fma(vcx[g], dao[off], fma(vcx[npts + g], dao[plane + off], vcx[2 * npts + g] * dao[2 * plane + off])));
                 else
@@ -1178,14 +816,19 @@ __global__ __launch_bounds__(64 * BT) void xc_vmat_tau_kernel(int64_t npts, int 
         }
     };
 
+    // One product per pass of the loop.  Plain: one per step, and s is the step's first grid point.  TAU: four per step,
+    // and s counts the (step, operand) pairs.  (Written so that the plain loop runs over g0 itself: counted in steps it
+    // compiles to other, longer code.)
+    constexpr int DS = TAU ? 1 : 16;
+    const int64_t s_begin = TAU ? 0 : g_begin;
+    const int64_t s_end = TAU ? (g_begin < g_end ? 4 * ((g_end - g_begin + 15) / 16) : 0) : g_end;
     int buf = 0;
-    const int64_t nseq = g_begin < g_end ? 4 * ((g_end - g_begin + 15) / 16) : 0;  // (step, operand) pairs
-    if (nseq > 0) produce(0, g_begin, 0);
-    for (int64_t it = 0; it < nseq; ++it) {
-        const int64_t g0 = g_begin + 16 * (it >> 2);
-        const int op = (int)(it & 3);
+    if (s_begin < s_end) produce(0, g_begin, 0);
+    for (int64_t s = s_begin; s < s_end; s += DS) {
+        const int64_t g0 = TAU ? g_begin + 16 * (s >> 2) : s;
+        const int op = TAU ? (int)(s & 3) : 0;
         __syncthreads();  // hs[buf] is complete; hs[buf ^ 1] has been consumed
-        if (it + 1 < nseq) produce(buf ^ 1, g_begin + 16 * ((it + 1) >> 2), (int)((it + 1) & 3));
+        if (s + DS < s_end) produce(buf ^ 1, TAU ? g_begin + 16 * ((s + 1) >> 2) : s + 16, TAU ? (int)((s + 1) & 3) : 0);
         const double* src = op == 0 ? ao : dao + (op - 1) * plane;
         double a[4];
 #pragma unroll
@@ -1213,87 +856,207 @@ __global__ __launch_bounds__(64 * BT) void xc_vmat_tau_kernel(int64_t npts, int 
     }
 }
 
-}  // namespace
+// v[x][m][n] = sum_chunks (part[c][x][m][n] + part[c][x][n][m]), chunks in ascending order
+__global__ __launch_bounds__(256) void xc_vmat_reduce_kernel(int nao, int nchunk, const double* __restrict__ part,
+                                                             double* __restrict__ v) {
+    const int64_t n2 = (int64_t)nao * nao;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * n2) return;
+    const int x = (int)(i / n2);
+    const int64_t e = i - x * n2;
+    const int m = (int)(e / nao), n = (int)(e - (int64_t)m * nao);
+    const int64_t et = (int64_t)n * nao + m;
+    double s = 0.0;
+    for (int c = 0; c < nchunk; ++c) {
+        const double* p = part + ((int64_t)c * 2 + x) * n2;
+        s += p[e] + p[et];
+    }
+    v[i] = s;
+}
 
-extern "C" int nbx_xc_rho_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
-                              const double* d_dm, double* d_rho, double* d_grad, double* d_tau) {
-    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_dm && d_rho && d_grad && d_tau && npts >= 0 && nao >= 1);
+int vmat_bt(int64_t nao) {  // tiles per block side: the least padded 16 BT grid over nao, the larger BT on a tie
+    int best = 1;
+    int64_t best_pad = -1;
+    for (int bt = 1; bt <= 5; ++bt) {
+        const int64_t w = 16 * bt, pad = nbx_cdiv(nao, w) * w;
+        if (best_pad < 0 || pad <= best_pad) {
+            best = bt;
+            best_pad = pad;
+        }
+    }
+    return best;
+}
+
+int64_t vmat_chunk(int64_t npts, int64_t nao) {  // grid points per workgroup: enough workgroups to fill the chip
+    const int bt = vmat_bt(nao);
+    const int64_t nblk = nbx_cdiv(nao, 16 * bt);
+    int64_t chunk = 2048;
+    while (chunk > 256 && nbx_cdiv(npts, chunk) * nblk * nblk * 2 < 1024) chunk >>= 1;
+    return chunk;
+}
+
+size_t xc_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// nbx_xc_rho (d_tau = nullptr) and nbx_xc_rho_tau (`who` names the one for the error text); the other arguments are
+// checked here
+int xc_rho_launch(const char* who, nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
+                  const double* d_dm, double* d_rho, double* d_grad, double* d_tau) {
+    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_dm && d_rho && d_grad && npts >= 0 && nao >= 1);
     const int64_t kp = (nao + 3) & ~3ll;
     const size_t lds = (size_t)(2 * kp * 16) * sizeof(double);
     if (lds > 160 * 1024) {
-        nbx_set_error("nbx_xc_rho_tau: nao = %lld beyond the LDS-resident density slab (limit 640)", (long long)nao);
+        nbx_set_error("%s: nao = %lld beyond the LDS-resident density slab (limit 640)", who, (long long)nao);
         return NBX_E_UNSUPPORTED;
     }
     if (npts == 0) return NBX_OK;
-    const dim3 grid((unsigned)nbx_cdiv(npts, 64));
+    // [the ao fragments stay in registers: nao <= 160][tau]
+    static const decltype(&xc_rho_kernel<0, false>) kernels[2][2] = {{xc_rho_kernel<0, false>, xc_rho_kernel<0, true>},
+                                                                     {xc_rho_kernel<40, false>, xc_rho_kernel<40, true>}};
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xc_rho_tau_kernel<40>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xc_rho_tau_kernel<0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (int i = 0; i < 4; ++i)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[i >> 1][i & 1]),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    if (kp <= 160)
-        hipLaunchKernelGGL(xc_rho_tau_kernel<40>, grid, dim3(256), lds, ctx->stream, npts, (int)nao, d_ao, d_dao, d_dm, d_rho,
-                           d_grad, d_tau);
-    else
-        hipLaunchKernelGGL(xc_rho_tau_kernel<0>, grid, dim3(256), lds, ctx->stream, npts, (int)nao, d_ao, d_dao, d_dm, d_rho,
-                           d_grad, d_tau);
+    hipLaunchKernelGGL(kernels[kp <= 160][d_tau != nullptr], dim3((unsigned)nbx_cdiv(npts, 64)), dim3(256), lds, ctx->stream,
+                       npts, (int)nao, d_ao, d_dao, d_dm, d_rho, d_grad, d_tau);
     NBX_LAUNCH_CHECK();
     return NBX_OK;
 }
 
-extern "C" int nbx_xc_functional_mgga(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
-                                      const double* d_tau, const double* d_w, double rho_floor, double* d_vr, double* d_vec,
-                                      double* d_vt, double* d_sums, void* d_work, size_t work_bytes) {
-    NBX_CHECK_ARG(code == NBX_XC_TPSS || code == NBX_XC_TPSSH);
-    NBX_CHECK_ARG(ctx && d_rho && d_grad && d_tau && d_w && d_vr && d_vec && d_vt && d_sums && d_work && npts >= 0);
+}  // namespace
+
+extern "C" int nbx_xc_rho(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
+                          const double* d_dm, double* d_rho, double* d_grad) {
+    return xc_rho_launch("nbx_xc_rho", ctx, npts, nao, d_ao, d_dao, d_dm, d_rho, d_grad, nullptr);
+}
+
+extern "C" int nbx_xc_rho_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
+                              const double* d_dm, double* d_rho, double* d_grad, double* d_tau) {
+    NBX_CHECK_ARG(d_tau);
+    return xc_rho_launch("nbx_xc_rho_tau", ctx, npts, nao, d_ao, d_dao, d_dm, d_rho, d_grad, d_tau);
+}
+
+extern "C" size_t nbx_xc_functional_worksize(int64_t npts) {
+    return npts <= 0 ? 256 : xc_align256((size_t)(2 * nbx_cdiv(npts, XC_FN_THREADS)) * sizeof(double));
+}
+
+namespace {
+
+// nbx_xc_functional (codes 0 .. 8), nbx_xc_functional_rs (16, 17: the only ones that read omega) and
+// nbx_xc_functional_mgga (32, 33: the only ones that read d_tau and write d_vt); the other arguments are checked here
+int xc_functional_launch(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho, const double* d_grad,
+                         const double* d_tau, const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_vt,
+                         double* d_sums, void* d_work, size_t work_bytes) {
+    NBX_CHECK_ARG(ctx && d_rho && d_grad && d_w && d_vr && d_vec && d_sums && d_work && npts >= 0);
     NBX_CHECK_ARG(rho_floor > 0.0 && work_bytes >= nbx_xc_functional_worksize(npts));
     if (npts == 0) return nbx_memset(ctx, d_sums, 0, 2 * sizeof(double));
     const int64_t nblk = nbx_cdiv(npts, XC_FN_THREADS);
     NBX_CHECK_ARG(nblk < (1ll << 30));
     double* part = static_cast<double*>(d_work);
-    if (code == NBX_XC_TPSS)
-        hipLaunchKernelGGL(xc_functional_mgga_kernel<NBX_XC_TPSS>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,
-                           d_rho, d_grad, d_tau, d_w, rho_floor, d_vr, d_vec, d_vt, part);
-    else
-        hipLaunchKernelGGL(xc_functional_mgga_kernel<NBX_XC_TPSSH>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,
-                           d_rho, d_grad, d_tau, d_w, rho_floor, d_vr, d_vec, d_vt, part);
+#define NBX_XC_FN(CODE_)                                                                                                  \
+    case CODE_:                                                                                                           \
+        hipLaunchKernelGGL(xc_functional_kernel<CODE_>, dim3((unsigned)nblk), dim3(XC_FN_THREADS), 0, ctx->stream, npts,  \
+                           d_rho, d_grad, d_w, rho_floor, omega, d_vr, d_vec, part, d_tau, d_vt);                         \
+        break
+    switch (code) {
+        NBX_XC_FN(NBX_XC_SLATER);
+        NBX_XC_FN(NBX_XC_LDA_VWN_RPA);
+        NBX_XC_FN(NBX_XC_LDA_VWN5);
+        NBX_XC_FN(NBX_XC_B3LYP);
+        NBX_XC_FN(NBX_XC_LDA_PW_MOD);
+        NBX_XC_FN(NBX_XC_PBE);
+        NBX_XC_FN(NBX_XC_PBEH);
+        NBX_XC_FN(NBX_XC_BLYP);
+        NBX_XC_FN(NBX_XC_B3LYP5);
+        NBX_XC_FN(NBX_XC_CAM_B3LYP);
+        NBX_XC_FN(NBX_XC_LC_BLYP);
+        NBX_XC_FN(NBX_XC_TPSS);
+        default: NBX_XC_FN(NBX_XC_TPSSH);
+    }
+#undef NBX_XC_FN
     NBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(xc_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, (int)nblk, part, d_sums);
     NBX_LAUNCH_CHECK();
     return NBX_OK;
 }
 
+}  // namespace
+
+extern "C" int nbx_xc_functional(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
+                                 const double* d_w, double rho_floor, double* d_vr, double* d_vec, double* d_sums, void* d_work,
+                                 size_t work_bytes) {
+    NBX_CHECK_ARG(code >= NBX_XC_SLATER && code <= NBX_XC_B3LYP5);
+    return xc_functional_launch(ctx, code, 0.0, npts, d_rho, d_grad, nullptr, d_w, rho_floor, d_vr, d_vec, nullptr, d_sums, d_work,
+                                work_bytes);
+}
+
+extern "C" int nbx_xc_functional_rs(nbx_ctx* ctx, int code, double omega, int64_t npts, const double* d_rho,
+                                    const double* d_grad, const double* d_w, double rho_floor, double* d_vr, double* d_vec,
+                                    double* d_sums, void* d_work, size_t work_bytes) {
+    NBX_CHECK_ARG(code == NBX_XC_CAM_B3LYP || code == NBX_XC_LC_BLYP);
+    NBX_CHECK_ARG(omega >= 0.0 && omega < 1.0e150);  // (finite; 0 is the plain B88: F(0) = 1)
+    return xc_functional_launch(ctx, code, omega, npts, d_rho, d_grad, nullptr, d_w, rho_floor, d_vr, d_vec, nullptr, d_sums, d_work,
+                                work_bytes);
+}
+
+extern "C" int nbx_xc_functional_mgga(nbx_ctx* ctx, int code, int64_t npts, const double* d_rho, const double* d_grad,
+                                      const double* d_tau, const double* d_w, double rho_floor, double* d_vr, double* d_vec,
+                                      double* d_vt, double* d_sums, void* d_work, size_t work_bytes) {
+    NBX_CHECK_ARG(code == NBX_XC_TPSS || code == NBX_XC_TPSSH);
+    NBX_CHECK_ARG(d_tau && d_vt);
+    return xc_functional_launch(ctx, code, 0.0, npts, d_rho, d_grad, d_tau, d_w, rho_floor, d_vr, d_vec, d_vt, d_sums, d_work,
+                                work_bytes);
+}
+
+extern "C" size_t nbx_xc_vmat_worksize(int64_t npts, int64_t nao) {
+    if (npts <= 0 || nao <= 0) return 256;
+    const int64_t nchunk = nbx_cdiv(npts, vmat_chunk(npts, nao));
+    return xc_align256((size_t)(nchunk * 2 * nao * nao) * sizeof(double));
+}
+
 extern "C" size_t nbx_xc_vmat_tau_worksize(int64_t npts, int64_t nao) { return nbx_xc_vmat_worksize(npts, nao); }
 
-extern "C" int nbx_xc_vmat_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
-                               const double* d_vr, const double* d_vec, const double* d_vt, double* d_vxc, void* d_work,
-                               size_t work_bytes) {
-    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_vr && d_vec && d_vt && d_vxc && npts >= 0 && nao >= 1 && nao <= (1 << 15));
+namespace {
+
+// nbx_xc_vmat (d_vt = nullptr) and nbx_xc_vmat_tau; the other arguments are checked here
+int xc_vmat_launch(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao, const double* d_vr,
+                   const double* d_vec, const double* d_vt, double* d_vxc, void* d_work, size_t work_bytes) {
+    NBX_CHECK_ARG(ctx && d_ao && d_dao && d_vr && d_vec && d_vxc && npts >= 0 && nao >= 1 && nao <= (1 << 15));
     const int64_t n2 = nao * nao;
     if (npts == 0) return nbx_memset(ctx, d_vxc, 0, (size_t)(2 * n2) * sizeof(double));
-    NBX_CHECK_ARG(d_work && work_bytes >= nbx_xc_vmat_tau_worksize(npts, nao));
+    NBX_CHECK_ARG(d_work && work_bytes >= nbx_xc_vmat_worksize(npts, nao));
     const int bt = vmat_bt(nao);
     const int64_t chunk = vmat_chunk(npts, nao), nchunk = nbx_cdiv(npts, chunk), nblk = nbx_cdiv(nao, 16 * bt);
     NBX_CHECK_ARG(nblk * nblk <= 65535 && nchunk < (1ll << 31));
     double* part = static_cast<double*>(d_work);
     const dim3 grid((unsigned)nchunk, (unsigned)(nblk * nblk), 2);
-#define NBX_VMAT_TAU(BT_)                                                                                                  \
-    hipLaunchKernelGGL(xc_vmat_tau_kernel<BT_>, grid, dim3(64 * BT_), 0, ctx->stream, npts, (int)nao, chunk, (int)nblk, d_ao, \
-                       d_dao, d_vr, d_vec, d_vt, part)
-    switch (bt) {
-        case 1: NBX_VMAT_TAU(1); break;
-        case 2: NBX_VMAT_TAU(2); break;
-        case 3: NBX_VMAT_TAU(3); break;
-        case 4: NBX_VMAT_TAU(4); break;
-        default: NBX_VMAT_TAU(5); break;
-    }
-#undef NBX_VMAT_TAU
+    // [bt - 1][tau]
+    static const decltype(&xc_vmat_kernel<1, false>) kernels[5][2] = {{xc_vmat_kernel<1, false>, xc_vmat_kernel<1, true>},
+                                                                      {xc_vmat_kernel<2, false>, xc_vmat_kernel<2, true>},
+                                                                      {xc_vmat_kernel<3, false>, xc_vmat_kernel<3, true>},
+                                                                      {xc_vmat_kernel<4, false>, xc_vmat_kernel<4, true>},
+                                                                      {xc_vmat_kernel<5, false>, xc_vmat_kernel<5, true>}};
+    hipLaunchKernelGGL(kernels[bt - 1][d_vt != nullptr], grid, dim3(64 * bt), 0, ctx->stream, npts, (int)nao, chunk, (int)nblk,
+                       d_ao, d_dao, d_vr, d_vec, part, d_vt);
     NBX_LAUNCH_CHECK();
     hipLaunchKernelGGL(xc_vmat_reduce_kernel, dim3((unsigned)nbx_cdiv(2 * n2, 256)), dim3(256), 0, ctx->stream, (int)nao,
                        (int)nchunk, part, d_vxc);
     NBX_LAUNCH_CHECK();
     return NBX_OK;
+}
+
+}  // namespace
+
+extern "C" int nbx_xc_vmat(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
+                           const double* d_vr, const double* d_vec, double* d_vxc, void* d_work, size_t work_bytes) {
+    return xc_vmat_launch(ctx, npts, nao, d_ao, d_dao, d_vr, d_vec, nullptr, d_vxc, d_work, work_bytes);
+}
+
+extern "C" int nbx_xc_vmat_tau(nbx_ctx* ctx, int64_t npts, int64_t nao, const double* d_ao, const double* d_dao,
+                               const double* d_vr, const double* d_vec, const double* d_vt, double* d_vxc, void* d_work,
+                               size_t work_bytes) {
+    NBX_CHECK_ARG(d_vt);
+    return xc_vmat_launch(ctx, npts, nao, d_ao, d_dao, d_vr, d_vec, d_vt, d_vxc, d_work, work_bytes);
 }

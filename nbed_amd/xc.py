@@ -803,25 +803,21 @@ class XCProvider:
         """One evaluation on libnbx: nbx_xc_rho (densities and gradients, both spins, c = ao D on the matrix cores),
         nbx_xc_functional (analytic energy density and derivatives, weights folded in, E_xc reduced on the device),
         nbx_xc_vmat (the potential matrix with its ``half`` factor built on the fly).  Three kernels and two small
-        reductions per evaluation; the host sees E_xc, the electron count and the (2, nao, nao) result."""
+        reductions per evaluation; the host sees E_xc, the electron count and the (2, nao, nao) result.  A meta-GGA
+        takes the tau forms of the three: nbx_xc_rho_tau adds tau = 1/2 sum_a diag(dao_a D dao_a^T) to the density pass,
+        nbx_xc_functional_mgga returns w dE/dtau as well, nbx_xc_vmat_tau adds 1/4 v_tau dao_a to the operand."""
         from ._nbx import XC_CODES, XC_MGGA_CODES, XC_RS_CODES
 
+        mgga = self.xc in XC_MGGA_CODES
         dmd = be.asarray(0.5 * (dm + dm.transpose(0, 2, 1)))
-        if self.xc in XC_MGGA_CODES:
-            # the meta-GGA chain: nbx_xc_rho_tau adds tau = 1/2 sum_a diag(dao_a D dao_a^T) to the density pass,
-            # nbx_xc_functional_mgga returns w dE/dtau as well, nbx_xc_vmat_tau adds 1/4 v_tau dao_a to the operand
-            rho, grad, tau = be.xc_rho_tau(self._ao, self._dao, dmd)
-            vr, vec, vt, sums = be.xc_functional_mgga(XC_MGGA_CODES[self.xc], rho, grad, tau, self._w, self.RHO_FLOOR)
-            vxc = be.xc_vmat_tau(self._ao, self._dao, vr, vec, vt)
-            sums_h = be.to_host(sums)
-            self.nelec_last = float(sums_h[1])
-            return float(sums_h[0]), be.to_host(vxc)
-        rho, grad = be.xc_rho(self._ao, self._dao, dmd)
-        if self.xc in XC_RS_CODES:
-            vr, vec, sums = be.xc_functional_rs(XC_RS_CODES[self.xc], self.omega, rho, grad, self._w, self.RHO_FLOOR)
+        dens = (be.xc_rho_tau if mgga else be.xc_rho)(self._ao, self._dao, dmd)  # (rho, grad[, tau])
+        if mgga:
+            *derivs, sums = be.xc_functional_mgga(XC_MGGA_CODES[self.xc], *dens, self._w, self.RHO_FLOOR)
+        elif self.xc in XC_RS_CODES:
+            *derivs, sums = be.xc_functional_rs(XC_RS_CODES[self.xc], self.omega, *dens, self._w, self.RHO_FLOOR)
         else:
-            vr, vec, sums = be.xc_functional(XC_CODES[self.xc], rho, grad, self._w, self.RHO_FLOOR)
-        vxc = be.xc_vmat(self._ao, self._dao, vr, vec)
+            *derivs, sums = be.xc_functional(XC_CODES[self.xc], *dens, self._w, self.RHO_FLOOR)
+        vxc = (be.xc_vmat_tau if mgga else be.xc_vmat)(self._ao, self._dao, *derivs)  # derivs: (vr, vec[, vt])
         sums_h = be.to_host(sums)
         self.nelec_last = float(sums_h[1])
         return float(sums_h[0]), be.to_host(vxc)
