@@ -17,6 +17,10 @@
 //    and differ by rounding noise ~ eps ||A||; E_ij + E_ji = R_ij then holds only to noise / gap, and the updated
 //    vectors lose orthonormality at that level (1e-9 where ||A|| = 1e6) instead of O(E^2) -- which a solver that
 //    takes them as an orthonormal start (the Jacobi fallback of the next cycle) turns into residuals of 1e-3.
+//    G is symmetrised the same way, G_ij <- (G_ij + G_ji) / 2: in the pencil G = C^T (C^T S)^T, and G_ij, G_ji are
+//    different dot products too; E_ij + E_ji = R_ij then fails by lambda (G_ij - G_ji) / gap: first order in
+//    noise / gap again (3e-9 of |C^T S C - I| beside a pair at a gap of 1e-10 in the float64 model of
+//    tests/geig_cases.py).
 //  * omega is taken per pair: omega_ij = 2 (||N||_F + max(|lambda_i|, |lambda_j|) ||R||_F), N_ij = the smaller in
 //    magnitude of the two one-sided residuals S_ij + lambda_j R_ij and S_ij + lambda_i R_ij (= S_ij when R = 0).
 //    With the global norms a loss of orthonormality of 1e-8 among the levels at 1e6 (harmless: their own gaps are
@@ -54,9 +58,10 @@ constexpr double RF_NOISE = 8.0 * 1.1102230246251565e-16;
 // |V^T V - I| up to 4e-7.  nbx_eigh_refine therefore takes the noise exit only below RF_NOISE_EMAX: three partners
 // at 5e-7 cost a level 0.75e-12, what the Newton-Schulz step of the cold route leaves (eigh_tridiag.hip: a Gram defect
 // of 1e-6 squared); above it the matrix goes to the Jacobi fallback, which rotates such pairs exactly.  The stalled
-// mu-shifted matrices sit at 1e-7.  nbx_geig_refine, which has no fallback behind it, keeps RF_NOISE_EMAX_PENCIL.
+// mu-shifted matrices sit at 1e-7.  nbx_geig_refine takes the exit below the same limit (it had 1e-3, and delivered
+// pencils with a pair at a gap of 1e-10 at |C^T S C - I| = 5e-6, status 1001); it has no fallback behind it, so above
+// the limit it REFUSES (status <= 0) and the SCF loops repeat the cycle on the guarded solver.
 constexpr double RF_NOISE_EMAX = 5.0e-7;
-constexpr double RF_NOISE_EMAX_PENCIL = 1.0e-3;
 constexpr int RF_PART = 6;  // doubles each workgroup publishes per matrix
 
 // G = X^T X, S = X^T A X  ->  Ep = I + E, lambda, status.  RF_WGS workgroups per matrix (grid
@@ -217,23 +222,25 @@ __global__ __launch_bounds__(RF_THREADS) void refine_e_kernel(int N, const doubl
     // ---- phase 2: E
     double emax = 0.0, cmax = 0.0, nmax = 0.0;
     for (int e0 = first; e0 < total; e0 += stride * RF_UNROLL) {
-        double sv[RF_UNROLL], gv[RF_UNROLL], st[RF_UNROLL];
+        double sv[RF_UNROLL], gv[RF_UNROLL], st[RF_UNROLL], gt[RF_UNROLL];
         int ri[RF_UNROLL];
 #pragma unroll
         for (int u = 0; u < RF_UNROLL; ++u) {
             const int e = e0 + u * stride;
             const bool in = e < total;
             ri[u] = in ? row_of(e) : 0;
+            const int64_t et = (int64_t)(e - ri[u] * N) * N + ri[u];
             sv[u] = in ? S[e] : 0.0;
             gv[u] = in ? G[e] : 0.0;
-            st[u] = in ? S[(int64_t)(e - ri[u] * N) * N + ri[u]] : 0.0;  // S_ji (the matrix lives in L2)
+            st[u] = in ? S[et] : 0.0;  // S_ji (the matrix lives in L2)
+            gt[u] = in ? G[et] : 0.0;  // G_ji
         }
 #pragma unroll
         for (int u = 0; u < RF_UNROLL; ++u) {
             const int e = e0 + u * stride;
             if (e < total) {
                 const int i = ri[u], j = e - i * N;
-                const double sx = 0.5 * (sv[u] + st[u]), g = gv[u];
+                const double sx = 0.5 * (sv[u] + st[u]), g = 0.5 * (gv[u] + gt[u]);
                 double ev;
                 if (i == j) {
                     ev = 0.5 * (1.0 - g);
@@ -283,9 +290,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_e_kernel(int N, const doubl
                 cmax = fmax(cmax, peek(part + w * RF_PART + 4));
                 nmax = fmax(nmax, peek(part + w * RF_PART + 5));
             }
-            // (A == nullptr: the pencil, nbx_geig_refine)
-            const bool at_noise = nmax <= RF_NOISE * sqrt((double)N) * na &&
-                                  emax < (A != nullptr ? RF_NOISE_EMAX : RF_NOISE_EMAX_PENCIL);
+            const bool at_noise = nmax <= RF_NOISE * sqrt((double)N) * na && emax < RF_NOISE_EMAX;
             int st = 0;
             if (!(emax < RF_GIVE_UP)) st = -1;  // also NaN
             else if ((emax < RF_TOL || at_noise) && cmax <= RF_CLUSTER_NOISE * na) st = iter + 1;

@@ -33,7 +33,7 @@ The kernels' constants, restated.
                    accepted: quality_status_kernel (eigh_tridiag.hip:972, device verdict, 64 <= N <= 196) and
                    nbx_eigh_warm_ex (eigh.hip:383, host verdict, N > 196).  It is the LOOSEST stopping rule of all
                    routes: the Jacobi kernels rotate until a_pq^2 <= eps^2 |a_pp a_qq| (eigh_lds.hip:200), and the
-                   refinement accepts at max |E| < RF_TOL = 3e-8 (eigh_refine.hip:41), which leaves ~RF_TOL^2 = 9e-16.
+                   refinement accepts at max |E| < RF_TOL = 3e-8 (eigh_refine.hip:45), which leaves ~RF_TOL^2 = 9e-16.
   GRAM = 1e-6      the Gram defect of the inverse-iteration vectors up to which ONE Newton-Schulz step
                    V <- V (3 I - V^T V) / 2 is taken (eigh_tridiag.hip:969, :1035, :927): it leaves 0.75 GRAM^2.
   u = N eps        the backward-error model of matfn_cases (eps = 2^-52).
@@ -67,7 +67,7 @@ from matfn_cases import CERTIFICATE, EPS, LD, compose, householder_q, jittered_g
 # ------------------------------------------------------------------ the kernels' constants, restated (module docstring)
 ACCEPT = 1.0e-13     # eigh_tridiag.hip:972, eigh.hip:383
 GRAM = 1.0e-6        # eigh_tridiag.hip:969, :1035, :927
-RF_TOL = 3.0e-8      # eigh_refine.hip:41
+RF_TOL = 3.0e-8      # eigh_refine.hip:45
 GROUP = 1.0e-7       # x nrm: levels closer than this to a neighbour are judged together
 SUBSPACE_MAX = 1.0e-4
 
