@@ -48,8 +48,11 @@ __global__ __launch_bounds__(256) void df_rho_kernel(const double* __restrict__ 
 }
 
 // j[e] (+)= sum_{l < ls} rho[l] * b[l][e]       two doubles per thread, the slab streamed once
+// vec2 (uniform over the launch): every b + l * n2 + e is 16-byte aligned -- n2 even and b aligned -- and e + 1 < n2 for
+// every thread that gets here, so the pair is one 16-byte load.  With an odd n2 the slices of odd l start 8 bytes off:
+// two 8-byte loads per pair there, and the last thread has a single element.
 __global__ __launch_bounds__(256) void df_j_kernel(const double* __restrict__ b, const double* __restrict__ rho, int ls,
-                                                   int64_t n2, double* __restrict__ j, int accumulate) {
+                                                   int64_t n2, double* __restrict__ j, int accumulate, int vec2) {
     __shared__ double r[DF_LS];
     if (threadIdx.x < ls) r[threadIdx.x] = rho[threadIdx.x];
     __syncthreads();
@@ -59,12 +62,13 @@ __global__ __launch_bounds__(256) void df_j_kernel(const double* __restrict__ b,
     double2 acc = make_double2(0.0, 0.0);
     for (int l = 0; l < ls; ++l) {
         const double* p = b + (int64_t)l * n2 + e;
-        if (two) {
+        if (vec2) {
             const double2 v = *reinterpret_cast<const double2*>(p);
             acc.x = fma(r[l], v.x, acc.x);
             acc.y = fma(r[l], v.y, acc.y);
         } else {
             acc.x = fma(r[l], p[0], acc.x);
+            if (two) acc.y = fma(r[l], p[1], acc.y);
         }
     }
     if (accumulate) {
@@ -190,7 +194,7 @@ int nbx_jk_df(nbx_ctx* ctx, int64_t nao, int64_t naux, const double* d_b, int64_
                       ndm);
         if (rc != NBX_OK) return rc;
         hipLaunchKernelGGL(df_j_kernel, dim3((unsigned)nbx_cdiv(n2, 512)), dim3(256), 0, ctx->stream, bs, rho, (int)ls, n2, d_jk,
-                           l0 > 0 ? 1 : 0);
+                           l0 > 0 ? 1 : 0, (n2 % 2 == 0 && (reinterpret_cast<uintptr_t>(bs) & 15) == 0) ? 1 : 0);
         NBX_LAUNCH_CHECK();
     }
     return NBX_OK;
