@@ -52,6 +52,7 @@ extern "C" {
 #define NBX_E_NOMEM (-3)    /* workspace too small / allocation failed */
 #define NBX_E_NOCONV (-4)   /* iterative kernel hit its sweep limit (results still written) */
 #define NBX_E_UNSUPPORTED (-5)
+#define NBX_E_INTERNAL (-6) /* a consistency check of the library on its own tables failed (a bug: the message says which) */
 
 typedef struct nbx_ctx nbx_ctx;
 

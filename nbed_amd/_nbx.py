@@ -22,6 +22,7 @@ NBX_E_HIP = -2
 NBX_E_NOMEM = -3
 NBX_E_NOCONV = -4
 NBX_E_UNSUPPORTED = -5
+NBX_E_INTERNAL = -6
 LOC_PM, LOC_BOYS = 0, 1  # nbx_loc_worksize kinds (NBX_LOC_PM, NBX_LOC_BOYS)
 
 HUZ_JK_PACKED, HUZ_JK_SYM = 0, 1

@@ -19,6 +19,7 @@
 // its blocks plus a constant -- on the host (m8_ranges) and handed to the kernels as an argument, not at equal tile counts.
 // Roles, ring, LDS-DMA, X operands, fixed-order partial rows: jk_m4.hip / jk_mx.hip.  Measurements, ablations and what was
 // tried and dropped: profiles/r04/jk_m8_measurements.txt, DESIGN.md section 9 (4).
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -113,7 +114,8 @@ template <int NB, int NDM, int LP>
 __global__ __launch_bounds__(M8_THREADS, 1) void jk_m8_kernel(const double* __restrict__ packed, const double* __restrict__ dm,
                                                               const double* __restrict__ wtab, double* __restrict__ jfull,
                                                               double* __restrict__ kpart1, double* __restrict__ kpart2,
-                                                              double* __restrict__ jpart, int64_t t_begin, M8Ranges rg, int S) {
+                                                              double* __restrict__ jpart, int64_t t_begin, M8Ranges rg, M8Tables tb,
+                                                              int S) {
     using G_ = M8Geom<NB, LP>;
     constexpr int N = G_::N, NG = G_::NG, NCH = G_::NCH, BUF = G_::BUF, PT = M4_PROD_THREADS, RING = G_::RING, AHEAD = RING - 1;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -129,9 +131,11 @@ __global__ __launch_bounds__(M8_THREADS, 1) void jk_m8_kernel(const double* __re
     const int64_t T0 = t_begin + rg.first[blockIdx.x];
     const int64_t T_end = t_begin + rg.first[blockIdx.x + 1];
     if (T0 >= T_end) return;  // uniform for the whole workgroup
-    const int p_first = m8_tri_row(T0);
     const int ntile = (int)(T_end - T0);
-    const double* tile0 = packed + (m8_tile_offset<G_>(T0) - m8_tile_offset<G_>(t_begin));
+    // (from the host's tables, M8Tables: nothing is computed between the launch and the first request for a tile -- the
+    //  square root of m8_tri_row and two m8_tile_offset walks over the rows in every wave were 8 us of this kernel)
+    const int p_first = m8_byte(tb.pfirst, (int)blockIdx.x);
+    const double* tile0 = packed + 16 * (int64_t)tb.tile_off[blockIdx.x];
 
     // X of a tile: xs[n][c] = D^{c / 2}[c & 1 ? p : q][n]  (NDM = 1: columns 2, 3 are zero); by the CONSUMER waves.  The two
     // q columns are new with every tile; the two p columns only when the row has changed since the buffer was last
@@ -189,19 +193,6 @@ __global__ __launch_bounds__(M8_THREADS, 1) void jk_m8_kernel(const double* __re
         m8_d2 wres[NCH][LP];  // Dtot' of the whole tile (the same for every tile)
         double j2x[NCH][LP], j2y[NCH][LP];  // J[rs] += (pq|rs) D'[pq], summed over the tiles of the range
         double jacc = 0.0;
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int s = 0; s < LP; ++s) {
-                wres[k][s] = *reinterpret_cast<const m8_d2*>(wtab + 2 * ((k * LP + s) * PT + ptid));
-                j2x[k][s] = j2y[k][s] = 0.0;
-            }
-        if (ptid < 8) jred[ptid] = 0.0;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the table: nothing of the compiler's in the counter from here)
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int s = 0; s < LP; ++s) asm volatile("" : "+v"(wres[k][s]));  // (the compiler's own wait for the table: here, not behind the first chunk loads)
         // the chunk that goes into the ring next: chunk ik of tile it = (ip, iq), which has ink chunks and starts at itile
         int it = 0, ik = 0, ip = p, iq = q, ink = m8_nk<G_>(p);
         const double* itile = tile0;
@@ -244,7 +235,24 @@ __global__ __launch_bounds__(M8_THREADS, 1) void jk_m8_kernel(const double* __re
         };
 #pragma unroll
         for (int c = 0; c < AHEAD; ++c) issue_next();
-        m8_wait_vm<(AHEAD - 1) * LP>();  // my part of the first chunk
+        // The stream starts first and the table travels behind it, one trip for both (the table first and drained, then the
+        // chunks, was two).  The table's wait is for everything: the first chunk has landed with it, and what
+        // m8_wait_vm<(AHEAD - 1) LP> counts at every step from here on -- chunk loads only, in the order of their issue --
+        // is what is in the counter.  (Written out here: with the same statements in a lambda the compiler ran out of
+        // registers -- 256 and 104 bytes of scratch, reloaded inside the steps, against 242 and none.)
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+#pragma unroll
+            for (int s = 0; s < LP; ++s) {
+                wres[k][s] = *reinterpret_cast<const m8_d2*>(wtab + 2 * ((k * LP + s) * PT + ptid));
+                j2x[k][s] = j2y[k][s] = 0.0;
+            }
+        if (ptid < 8) jred[ptid] = 0.0;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the table: nothing of the compiler's in the counter from here)
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+#pragma unroll
+            for (int s = 0; s < LP; ++s) asm volatile("" : "+v"(wres[k][s]));  // (the compiler's own wait for the table: here, not behind a step's chunk loads)
         __syncthreads();
         int jslot = 0;  // ring slot of the chunk the consumers walk at this step
         // J[pq] of the tiles done: sixty-four of them wait in one register of wave 4 (lane i: tile jbase + i of the range) --
@@ -574,9 +582,22 @@ struct M8Plan {
 // The ranges of the workgroups: contiguous in the tile sequence, cut at equal COST: a tile costs its blocks plus a
 // constant for the hand-over of its rows (measured: 0.6 us per tile next to 1.05 us per chunk of 24 KB).
 // (NBX_M8_TC in the environment, in blocks: for measurements; read once)
+// With them M8Tables, filled along the same walk over the tiles -- a running offset and the row the walk is in -- and
+// then compared entry by entry with what jk_m8_kernel used to compute from first[] (m8_tile_offset, m8_tri_row);
+// *bad_out: the first entry that differs, as text (NULL: none).
+struct M8Split {
+    M8Ranges rg;
+    M8Tables tb;
+    char bad[96];
+};
+static_assert(sizeof(M8Ranges) + sizeof(M8Tables) + 16 * sizeof(void*) <= 4096 - 256, "the argument block of a kernel stays below 4 KB");
+
 template <class G>
-const M8Ranges& m8_ranges(int64_t p0, int64_t np, int* wgs_out) {
-    static thread_local M8Ranges rg;
+const M8Ranges& m8_ranges(int64_t p0, int64_t np, int* wgs_out, const M8Tables** tb_out = nullptr, const char** bad_out = nullptr) {
+    static_assert(G::N <= 256, "M8Tables: a row in a byte");
+    static thread_local M8Split sp;
+    M8Ranges& rg = sp.rg;
+    M8Tables& tb = sp.tb;
     static thread_local int64_t key_p0 = -1, key_np = -1;
     static thread_local int wgs = 0;
     if (key_p0 != p0 || key_np != np) {
@@ -593,14 +614,34 @@ const M8Ranges& m8_ranges(int64_t p0, int64_t np, int* wgs_out) {
         int w = 0;
         int64_t before = 0;
         int64_t trel = 0;
+        int64_t off = 0;  // doubles from the slab's first tile to this one
+        tb = M8Tables{};
         for (int p = (int)p0; p < (int)(p0 + np); ++p) {
             const int64_t c = cost_of_row(p);
             for (int q = 0; q <= p; ++q, ++trel) {
-                while (w < wgs && before * wgs >= (int64_t)w * total) rg.first[w++] = (int)trel;
+                while (w < wgs && before * wgs >= (int64_t)w * total) {
+                    tb.tile_off[w] = (int)(off / 16);
+                    m8_set_byte(tb.pfirst, w, p);
+                    rg.first[w++] = (int)trel;
+                }
                 before += c;
+                off += m8_len<G>(p);
             }
         }
         while (w <= M8_CUS) rg.first[w++] = (int)ntiles;
+        // the tables against the functions of first[] they stand for
+        sp.bad[0] = 0;
+        auto differs = [&](const char* what, int at, int64_t have, int64_t want) {
+            if (have != want && sp.bad[0] == 0)
+                snprintf(sp.bad, sizeof sp.bad, "%s[%d] = %lld, computed %lld", what, at, (long long)have, (long long)want);
+        };
+        const int64_t off0 = m8_tile_offset<G>(t_begin);
+        for (int v = 0; v < wgs; ++v) {
+            if (rg.first[v + 1] <= rg.first[v]) continue;  // (no tiles: its entries are not read)
+            const int64_t T = t_begin + rg.first[v];
+            differs("tile_off", v, 16 * (int64_t)tb.tile_off[v], m8_tile_offset<G>(T) - off0);
+            differs("pfirst", v, m8_byte(tb.pfirst, v), m8_tri_row(T));
+        }
         for (int k = 0; k < M8_MAXCH; ++k) rg.wmin[k] = wgs;
         for (int v = wgs - 1; v >= 0; --v) {
             if (rg.first[v + 1] <= rg.first[v]) continue;
@@ -611,6 +652,8 @@ const M8Ranges& m8_ranges(int64_t p0, int64_t np, int* wgs_out) {
         key_np = np;
     }
     *wgs_out = wgs;
+    if (tb_out != nullptr) *tb_out = &tb;
+    if (bad_out != nullptr) *bad_out = sp.bad[0] != 0 ? sp.bad : nullptr;
     return rg;
 }
 
@@ -650,7 +693,14 @@ int m8_run(nbx_ctx* ctx, int64_t p0, int64_t p1, const double* d_packed, const d
     const int64_t np = p1 - p0, N = G::N, n2 = N * N;
     const M8Plan pl = m8_plan<G>(p0, np, ndm);
     int wgs_;
-    const M8Ranges& rg = m8_ranges<G>(p0, np, &wgs_);
+    const M8Tables* tbp;
+    const char* bad;
+    const M8Ranges& rg = m8_ranges<G>(p0, np, &wgs_, &tbp, &bad);
+    const M8Tables& tb = *tbp;
+    if (bad != nullptr) {
+        nbx_set_error("nbx_jk_m8: the range tables of N = %lld, rows [%lld, %lld): %s", (long long)N, (long long)p0, (long long)p1, bad);
+        return NBX_E_INTERNAL;
+    }
     if (pl.lds_bytes > (size_t)M8_LDS_BYTES) {
         nbx_set_error("nbx_jk_m8: %zu bytes of LDS for N = %lld", pl.lds_bytes, (long long)N);
         return NBX_E_UNSUPPORTED;
@@ -691,10 +741,10 @@ int m8_run(nbx_ctx* ctx, int64_t p0, int64_t p1, const double* d_packed, const d
         }
         if (ndm == 2)
             hipLaunchKernelGGL((jk_m8_kernel<NB, 2, LP>), dim3((unsigned)pl.wgs), dim3(M8_THREADS), pl.lds_bytes, ctx->stream,
-                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, pl.S);
+                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, tb, pl.S);
         else
             hipLaunchKernelGGL((jk_m8_kernel<NB, 1, LP>), dim3((unsigned)pl.wgs), dim3(M8_THREADS), pl.lds_bytes, ctx->stream,
-                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, pl.S);
+                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, tb, pl.S);
     }
     NBX_LAUNCH_CHECK();
     {  // the two reductions in one launch

@@ -123,6 +123,18 @@ struct M8Ranges {
     int first[M8_CUS + 1];
     int wmin[M8_MAXCH];  // the first workgroup whose range has a tile with chunk k (the J partials of chunk k exist from there on)
 };
+// Where the range of workgroup w starts, made once per (N, p0, np) on the host where first[] is made (jk_m8.hip m8_ranges;
+// checked there against m8_tile_offset and m8_tri_row) and handed over the same way: 1.3 KB more of kernel argument
+// instead of, at every launch and in every wave of jk_m8_kernel, two walks over the rows for the address of the first
+// tile and a square root for its row.  The rows (N <= 148 < 256) are one-byte entries four to a word: a kernel argument
+// is read with scalar loads, and the scalar unit loads words -- a table of bytes indexed at run time becomes vector loads.
+static_assert(M8_CUS % 4 == 0, "one-byte entries, four to a word");
+struct M8Tables {
+    int tile_off[M8_CUS];         // of workgroup w's first tile, from the slab's first, in units of 16 doubles (every tile is a multiple)
+    unsigned pfirst[M8_CUS / 4];  // byte w: the row of workgroup w's first tile
+};
+__host__ __device__ __forceinline__ int m8_byte(const unsigned* a, int i) { return (int)((a[i >> 2] >> (8 * (i & 3))) & 255u); }
+inline void m8_set_byte(unsigned* a, int i, int v) { a[i >> 2] = (a[i >> 2] & ~(255u << (8 * (i & 3)))) | ((unsigned)v << (8 * (i & 3))); }
 // the workgroup that has tile t_begin + trel
 __device__ __forceinline__ int m8_wg_of(const M8Ranges& rg, int W, int trel) {
     int lo = 0, hi = W - 1;  // the largest w with first[w] <= trel
