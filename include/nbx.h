@@ -635,9 +635,12 @@ typedef struct nbx_huz_state {
     int64_t jk_p0, jk_p1;   /* this rank's slab rows [p0, p1) of the first AO index: 0, nao = the whole tensor;
                                p0 == p1 = an empty slab (contributes zero) */
     const double* d_eri;    /* NBX_HUZ_JK_SYM: slab rows [p0, p1) of the dense (N,N,N,N) tensor */
+    double* d_scal_partial; /* NBX_HUZ_PARTIAL_DOUBLES doubles, 16-byte aligned, or NULL: the partial sums of a cycle
+                               whose scalars are deferred (nbx_huz_cycle_carry); nothing else writes them */
 } nbx_huz_state;
 #define NBX_HUZ_JK_PACKED 0
 #define NBX_HUZ_JK_SYM 1
+#define NBX_HUZ_PARTIAL_DOUBLES 4096
 int nbx_huz_cycle(nbx_ctx* ctx, const nbx_huz_state* st, const double* d_dm_in, const double* d_c_in,
                   double* d_dm_out, double* d_c_out, double* d_v_out, double* d_w_out, double* d_hz_out, int mode,
                   int refine_iters, int diis_mode, int diis_slot, int diis_nd, int dts_ready, double* h_out,
@@ -654,6 +657,38 @@ int nbx_huz_cycle_jk(nbx_ctx* ctx, const nbx_huz_state* st, const double* d_dm_i
 int nbx_huz_cycle_post(nbx_ctx* ctx, const nbx_huz_state* st, const double* d_dm_in, const double* d_c_in,
                        double* d_dm_out, double* d_c_out, double* d_v_out, double* d_w_out, double* d_hz_out, int mode,
                        int refine_iters, int diis_mode, int diis_slot, int diis_nd, double* h_out, int* d_status_out);
+/* Deferred scalars.  The last stage of the kernel that stores a cycle's seven doubles to the host (the sums over the
+ * workgroups' partials, the host stores) is on the path to the next cycle's J/K build, which needs only the density
+ * and the Dtot' table from that kernel.  A cycle queued with defer != 0 stops at the partial sums (st->d_scal_partial) and describes what
+ * is left to do in *deferred_out; the caller hands that description to the NEXT nbx_huz_cycle_carry call as `carry`,
+ * whose J/K build takes the scalars to h_out of the deferred cycle in its first trip to memory (one wavefront; the same
+ * sums in the same order: bit-identical values, the ready word last), or to nbx_huz_scalars_flush when no cycle follows.
+ *   carry:        NULL or d_partial == NULL: nothing to carry -- no host slot but this cycle's own h_out is written.
+ *                 Where this call's build cannot carry (not the 8-fold packed kernel on the whole tensor) the scalars
+ *                 are flushed by a launch of their own ahead of the build.
+ *   defer:        a request.  Granted only where the next build could carry (the 8-fold packed kernel on the whole
+ *                 tensor, st->d_scal_partial given, a scalars launch the courier is written for); otherwise the cycle
+ *                 stores its scalars itself as nbx_huz_cycle does and deferred_out->d_partial is NULL.
+ *   deferred_out: required when defer != 0.  Nothing is remembered between calls: what is carried is what the caller
+ *                 states.  A deferred cycle's h_out receives nothing until a later call carries or flushes it, so a
+ *                 host that polls its ready word must have queued that call first.
+ * nbx_huz_cycle(..) is nbx_huz_cycle_carry(.., NULL, 0, NULL).                                                      */
+typedef struct nbx_scalars_courier {
+    const double* d_partial; /* nblocks x 4 partial sums of the scalars kernel (device, 16-byte aligned) */
+    int32_t nblocks;         /* workgroups of that launch */
+    int32_t nthreads;        /* threads per workgroup of that launch: 128 or 256 */
+    const int32_t* d_status; /* the status words that travel with the scalars (device) */
+    int32_t nstatus;
+    int32_t reserved;
+    double* h_out;           /* pinned (device-mapped) host memory: 4 + nstatus + 1 doubles */
+} nbx_scalars_courier;
+int nbx_huz_cycle_carry(nbx_ctx* ctx, const nbx_huz_state* st, const double* d_dm_in, const double* d_c_in,
+                        double* d_dm_out, double* d_c_out, double* d_v_out, double* d_w_out, double* d_hz_out, int mode,
+                        int refine_iters, int diis_mode, int diis_slot, int diis_nd, int dts_ready, double* h_out,
+                        int* d_status_out, const nbx_scalars_courier* carry, int defer,
+                        nbx_scalars_courier* deferred_out);
+/* The final stage of a deferred cycle as a launch of its own (one wavefront), queued on the context's stream. */
+int nbx_huz_scalars_flush(nbx_ctx* ctx, const nbx_scalars_courier* carry);
 
 /* ------------------------------------------------------------------ fused mu-shift SCF cycle
  * One cycle of the SCF the mu-shift embedding runs -- `embedded_scf.kernel()` at nbed/driver.py:533 on the hcore

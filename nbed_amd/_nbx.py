@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char, c_char_p, c_double, c_int, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 from pathlib import Path
 
 LIB_NAME = "libnbx.so"
@@ -70,6 +70,20 @@ class HuzState(ctypes.Structure):
         ("diis_space", c_int64), ("d_diis_xs", c_void_p), ("d_diis_es", c_void_p), ("d_diis_h", c_void_p),
         ("d_diis_coef", c_void_p), ("d_diis_xprev", c_void_p),
         ("jk_kind", c_int64), ("jk_p0", c_int64), ("jk_p1", c_int64), ("d_eri", c_void_p),
+        ("d_scal_partial", c_void_p),
+    ]
+
+
+HUZ_PARTIAL_DOUBLES = 4096  # NBX_HUZ_PARTIAL_DOUBLES: the doubles behind HuzState.d_scal_partial
+
+
+class ScalarsCourier(ctypes.Structure):
+    """``nbx_scalars_courier`` of include/nbx.h: what is left to do for a cycle whose scalars were deferred
+    (``nbx_huz_cycle_carry`` fills it; the next call, or ``nbx_huz_scalars_flush``, is handed it)."""
+
+    _fields_ = [
+        ("d_partial", c_void_p), ("nblocks", c_int32), ("nthreads", c_int32), ("d_status", c_void_p),
+        ("nstatus", c_int32), ("reserved", c_int32), ("h_out", c_void_p),
     ]
 
 
@@ -221,6 +235,9 @@ SIGNATURES = {
     "nbx_ao2mo_factor_expand": (c_int, [_P, c_int64, _P, _P]),
     "nbx_huz_cycle": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                               c_int, _P, _P]),
+    "nbx_huz_cycle_carry": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, _P, _P, POINTER(ScalarsCourier), c_int, POINTER(ScalarsCourier)]),
+    "nbx_huz_scalars_flush": (c_int, [_P, POINTER(ScalarsCourier)]),
     "nbx_huz_cycle_jk": (c_int, [_P, POINTER(HuzState), _P]),
     "nbx_mu_cycle": (c_int, [_P, POINTER(HuzState), _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                              c_int, _P, _P]),

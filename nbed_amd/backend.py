@@ -887,11 +887,16 @@ class HipBackend:
         st.diis_space = diis_space
         st.jk_kind = _nbx.HUZ_JK_PACKED if packed is not None else _nbx.HUZ_JK_SYM
         st.jk_p0, st.jk_p1 = p0, p1
+        # the partial sums of a cycle whose scalars are deferred (huz_cycle(defer=True)); h.deferred: what the next
+        # huz_cycle call or huz_flush has to carry to the host (the library keeps nothing between calls)
+        h.scal_partial = self.empty(_nbx.HUZ_PARTIAL_DOUBLES)
+        st.d_scal_partial = h.scal_partial.data_ptr()
+        h.deferred = None
         h.st = st
         return h
 
     def huz_cycle(self, h, dm_in, c_in, out, tracked: bool, refine_iters: int, diis_mode: int, diis_slot: int,
-                  diis_nd: int, dts_ready: bool, reduce=None):
+                  diis_nd: int, dts_ready: bool, reduce=None, defer: bool = False):
         """Queue one SCF cycle (nbx_huz_cycle) writing into the result set ``out``; returns the handle of
         its scalars + status words (read one cycle late, like ``huz_cycle_scalars_async``).  ``tracked``:
         False / 0 guarded eigensolve, True / 1 tracked refinement, 2 density by purification (``refine_iters``
@@ -899,16 +904,33 @@ class HipBackend:
 
         ``reduce``: for a run over several ranks -- a callable that sums the ranks' (3,N,N) J/K partials in
         place with a collective queued on this stream (``Shards.all_reduce``); the cycle is then two C calls
-        around it (nbx_huz_cycle_jk, nbx_huz_cycle_post), with the same look-ahead as the one-rank cycle."""
+        around it (nbx_huz_cycle_jk, nbx_huz_cycle_post), with the same look-ahead as the one-rank cycle.
+
+        ``defer``: a request to leave this cycle's scalars as partial sums on the device, for the J/K build of the
+        NEXT ``huz_cycle`` call on ``h`` (any mode) to take to the host on its way, or for ``huz_flush(h)`` -- the
+        handle's ``get()`` must not be called before one of the two has been queued.  Granted on the one-call route
+        with the whole tensor on the 8-fold packed kernel (nbx_huz_cycle_carry); elsewhere the cycle stores its
+        scalars itself, as without the request.  A call always carries what the previous one deferred."""
         h_out = self._pin_ring[self._pin_next][:7]
         h_out[6] = 0.0  # the kernel's "all stored" word
         self._pin_next = (self._pin_next + 1) % self._PIN_SLOTS
-        if reduce is None:
+        carry = getattr(h, "deferred", None)
+        if reduce is None and (defer or carry is not None):
+            left = _nbx.ScalarsCourier() if defer else None
+            h.deferred = None  # (whatever the call does with it, it is handed over once: a call that raises leaves nothing to flush)
+            self._call("nbx_huz_cycle_carry", ctypes.byref(h.st), self._p(dm_in), self._p(c_in), self._p(out["dm"]),
+                       self._p(out["c"]), self._p(out["v"]), self._p(out["w"]), self._p(out["hz"]), int(tracked),
+                       int(refine_iters), int(diis_mode), int(diis_slot), int(diis_nd), 1 if dts_ready else 0,
+                       self._p(h_out), self._p(out["status"]), ctypes.byref(carry) if carry is not None else None,
+                       1 if defer else 0, ctypes.byref(left) if defer else None)
+            h.deferred = left if (defer and left.d_partial) else None
+        elif reduce is None:
             self._call("nbx_huz_cycle", ctypes.byref(h.st), self._p(dm_in), self._p(c_in), self._p(out["dm"]),
                        self._p(out["c"]), self._p(out["v"]), self._p(out["w"]), self._p(out["hz"]), int(tracked),
                        int(refine_iters), int(diis_mode), int(diis_slot), int(diis_nd), 1 if dts_ready else 0,
                        self._p(h_out), self._p(out["status"]))
         else:
+            self.huz_flush(h)  # (the two-call route carries nothing)
             self._call("nbx_huz_cycle_jk", ctypes.byref(h.st), self._p(dm_in))
             reduce(h.jk)
             self._call("nbx_huz_cycle_post", ctypes.byref(h.st), self._p(dm_in), self._p(c_in), self._p(out["dm"]),
@@ -916,6 +938,14 @@ class HipBackend:
                        int(refine_iters), int(diis_mode), int(diis_slot), int(diis_nd), self._p(h_out),
                        self._p(out["status"]))
         return _PendingScalars(self.torch, None, 2, host=h_out)
+
+    def huz_flush(self, h):
+        """Queue the final stage of the cycle ``huz_cycle(h, .., defer=True)`` left deferred, as a launch of its own
+        (nbx_huz_scalars_flush): for a deferred cycle that no further cycle follows.  Nothing deferred: nothing queued."""
+        carry = getattr(h, "deferred", None)
+        if carry is not None:
+            h.deferred = None
+            self._call("nbx_huz_scalars_flush", ctypes.byref(carry))
 
     # ------------------------------------------------------------------ fused mu-shift SCF cycle (one call per cycle)
     def mu_cycle_state(self, nao, nelec, packed, h1e, s_b, x, eri=None, p0: int = 0, p1: int | None = None):

@@ -7,6 +7,7 @@
 #include "jk_m4_layout.h"
 #include "jk_packed.h"
 #include "jk_s4_layout.h"
+#include "scalars_courier.h"
 
 namespace {
 
@@ -360,6 +361,8 @@ __global__ void huz_scalars_kernel(const double* __restrict__ h, int h3d, const 
         }
     };
     if (out_final == nullptr) {
+        // (also the deferred form of the cycle's last kernel: the partials are all a courier needs to finish the sums
+        //  from a later kernel of the stream -- scalars_courier.h -- and the next build waits for no host store)
         store_dts();
         return;
     }
@@ -406,6 +409,13 @@ __global__ void huz_scalars_kernel(const double* __restrict__ h, int h3d, const 
         __hip_atomic_store(out_final + 4 + tail_n + dtail_n, 1.0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     store_dts();  // (this workgroup's part of the table, last of all)
+}
+
+// the final stage of a deferred huz_scalars_kernel on its own: for a deferred cycle that no J/K build follows
+__global__ __launch_bounds__(64) void scalars_flush_kernel(nbx_scalars_courier c) {
+    nbx_courier_regs r;
+    nbx_courier_request(c, (int)threadIdx.x, r);
+    nbx_courier_deliver(c, (int)threadIdx.x, r);
 }
 
 __global__ void axpby_kernel(int64_t n, double a, const double* __restrict__ x, double b, double* __restrict__ y) {
@@ -1318,7 +1328,7 @@ int nbx_huz_cycle_scalars_dts(nbx_ctx* ctx, int64_t nao, const double* d_hcore, 
                               double* d_dts) {
     NBX_CHECK_ARG(d_hz != nullptr);
     return nbx_cycle_scalars_launch(ctx, nao, d_hcore, hcore_ndim, d_vemb, d_vhf, d_hz, d_dm, d_dm_old, d_out, d_tail,
-                                    tail_n, d_dts, nullptr, 0);
+                                    tail_n, d_dts, nullptr, 0, nullptr);
 }
 
 }  // extern "C"
@@ -1328,8 +1338,9 @@ int nbx_huz_cycle_scalars_dts(nbx_ctx* ctx, int64_t nao, const double* d_hcore, 
 int nbx_cycle_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, int hcore_ndim, const double* d_vemb,
                              const double* d_vhf, const double* d_hz, const double* d_dm, const double* d_dm_old,
                              double* d_out, const int* d_tail, int64_t tail_n, double* d_dts, const double* d_dtail,
-                             int64_t dtail_n) {
+                             int64_t dtail_n, nbx_scalars_courier* deferred) {
     NBX_CHECK_ARG(ctx && d_hcore && d_vhf && d_dm && d_dm_old && d_out && nao > 0);
+    NBX_CHECK_ARG(deferred == nullptr || (deferred->d_partial != nullptr && dtail_n == 0));
     int nb4 = 0, lpt4 = 0, m4 = 0;  // the table's layout, in the order of the kernel that reads it (jk_packed.hip)
     NBX_CHECK_ARG(d_dts == nullptr || nbx_jk_dts_layout(nao, &nb4, &lpt4, &m4) > 0);  // the table exists where nbx_jk_dts_bytes > 0
     NBX_CHECK_ARG(tail_n >= 0 && tail_n <= 64 && (tail_n == 0 || d_tail != nullptr));
@@ -1339,17 +1350,22 @@ int nbx_cycle_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, i
     NBX_CHECK_ARG(route != NBX_CYCLE_SCALARS_REFUSED);
     const bool fine = route == NBX_CYCLE_SCALARS_T16;
     const int64_t g = nbx_cdiv(nao, fine ? 16 : TILE);
+    // deferred: the kernel stops at the partials, in the caller's slot, and *deferred says what is left to do
+    double* partial = deferred ? const_cast<double*>(deferred->d_partial) : ctx->d_scratch;
+    double* out_final = deferred ? nullptr : d_out;
+    if (deferred) NBX_CHECK_ARG(nbx_courier_covers((int)(g * g), fine ? 128 : TILE * 8, (int)tail_n));
     if (fine)
         hipLaunchKernelGGL(huz_scalars_kernel<16>, dim3((unsigned)g, (unsigned)g), dim3(16, 8), 0, ctx->stream, d_hcore,
-                           hcore_ndim == 3 ? 1 : 0, d_vemb, d_vhf, d_hz, d_dm, d_dm_old, (int)nao, ctx->d_scratch,
-                           d_out, d_tail, (int)tail_n, ctx->d_counters + NBX_COUNTERS - 1, d_dts, nb4, lpt4, m4, d_dtail,
+                           hcore_ndim == 3 ? 1 : 0, d_vemb, d_vhf, d_hz, d_dm, d_dm_old, (int)nao, partial,
+                           out_final, d_tail, (int)tail_n, ctx->d_counters + NBX_COUNTERS - 1, d_dts, nb4, lpt4, m4, d_dtail,
                            (int)dtail_n);
     else
         hipLaunchKernelGGL(huz_scalars_kernel<TILE>, dim3((unsigned)g, (unsigned)g), dim3(TILE, 8), 0, ctx->stream,
                            d_hcore, hcore_ndim == 3 ? 1 : 0, d_vemb, d_vhf, d_hz, d_dm, d_dm_old, (int)nao,
-                           ctx->d_scratch, d_out, d_tail, (int)tail_n, ctx->d_counters + NBX_COUNTERS - 1, d_dts, nb4,
+                           partial, out_final, d_tail, (int)tail_n, ctx->d_counters + NBX_COUNTERS - 1, d_dts, nb4,
                            lpt4, m4, d_dtail, (int)dtail_n);
     NBX_LAUNCH_CHECK();
+    if (deferred) nbx_courier_fill(deferred, (int)(g * g), fine ? 128 : TILE * 8, d_tail, (int)tail_n, d_out);
     return NBX_OK;
 }
 
@@ -1360,18 +1376,40 @@ int nbx_cycle_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, i
 int nbx_density_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, int hcore_ndim, const double* d_vemb,
                                const double* d_vhf, const double* d_hz, const double* d_c, int64_t nocc_a, int64_t nocc_b,
                                double* d_dm_out, const double* d_dm_old, double* d_out, const int* d_tail, int64_t tail_n,
-                               double* d_dts) {
+                               double* d_dts, nbx_scalars_courier* deferred) {
     NBX_CHECK_ARG(ctx && d_hcore && d_vhf && d_c && d_dm_out && d_dm_old && d_out && nao > 0);
+    NBX_CHECK_ARG(deferred == nullptr || deferred->d_partial != nullptr);
     if (!density_scalars_fused(nao, nocc_a, nocc_b)) return NBX_E_UNSUPPORTED;
     int nb4 = 0, lpt4 = 0, m4 = 0;
     NBX_CHECK_ARG(d_dts == nullptr || nbx_jk_dts_layout(nao, &nb4, &lpt4, &m4) > 0);
     NBX_CHECK_ARG(tail_n >= 0 && tail_n <= 64 && (tail_n == 0 || d_tail != nullptr));
     NBX_CHECK_ARG(hcore_ndim == 2 || hcore_ndim == 3);
     const int64_t g = nbx_cdiv(nao, 16);
+    if (deferred) NBX_CHECK_ARG(nbx_courier_covers((int)(g * g), 128, (int)tail_n));
     hipLaunchKernelGGL((huz_scalars_kernel<16, true>), dim3((unsigned)g, (unsigned)g), dim3(16, 8), 0, ctx->stream, d_hcore,
-                       hcore_ndim == 3 ? 1 : 0, d_vemb, d_vhf, d_hz, d_dm_out, d_dm_old, (int)nao, ctx->d_scratch, d_out,
+                       hcore_ndim == 3 ? 1 : 0, d_vemb, d_vhf, d_hz, d_dm_out, d_dm_old, (int)nao,
+                       deferred ? const_cast<double*>(deferred->d_partial) : ctx->d_scratch, deferred ? nullptr : d_out,
                        d_tail, (int)tail_n, ctx->d_counters + NBX_COUNTERS - 1, d_dts, nb4, lpt4, m4, nullptr, 0, d_c,
                        (int)nocc_a, (int)nocc_b, d_dm_out);
+    NBX_LAUNCH_CHECK();
+    if (deferred) nbx_courier_fill(deferred, (int)(g * g), 128, d_tail, (int)tail_n, d_out);
+    return NBX_OK;
+}
+
+// Whether a scalars launch for size nao can be deferred: a launch geometry the courier is written for
+bool nbx_cycle_scalars_deferrable(int64_t nao, int64_t tail_n) {
+    const int route = scalars_route(nao);
+    if (route == NBX_CYCLE_SCALARS_REFUSED) return false;
+    const bool fine = route == NBX_CYCLE_SCALARS_T16;
+    const int64_t g = nbx_cdiv(nao, fine ? 16 : TILE);
+    return g * g * 4 <= NBX_HUZ_PARTIAL_DOUBLES && nbx_courier_covers((int)(g * g), fine ? 128 : TILE * 8, (int)tail_n);
+}
+
+// The final stage of a deferred scalars kernel as a launch of its own: one wavefront (scalars_courier.h)
+extern "C" int nbx_huz_scalars_flush(nbx_ctx* ctx, const nbx_scalars_courier* carry) {
+    NBX_CHECK_ARG(ctx && carry);
+    NBX_CHECK_ARG(nbx_courier_valid(*carry));
+    hipLaunchKernelGGL(scalars_flush_kernel, dim3(1), dim3(64), 0, ctx->stream, *carry);
     NBX_LAUNCH_CHECK();
     return NBX_OK;
 }

@@ -26,6 +26,7 @@
 #include "jk_m8_layout.h"
 #include "jk_m4_walk.h"
 #include "jk_packed.h"
+#include "scalars_courier.h"
 
 #pragma clang diagnostic ignored "-Winline-asm"
 
@@ -110,12 +111,16 @@ __global__ __launch_bounds__(256) void m8_weights_kernel(const double* __restric
 // kpart2[(T - t_begin) NDM + x][N]: row-q partial of tile T (q < p; columns <= p);
 // jfull (N, N): J[p][q] = J[q][p] = the dot-product half of J for the tiles visited;
 // jpart[w][NCH LP 512]: workgroup w's AXPY half of J, in the staging order
+// cr: the scalars of the PREVIOUS SCF cycle, left as partial sums by a deferred huz_scalars_kernel (scalars_courier.h), or
+// null pointers: nothing to carry.  The first walking wave of workgroup 0 takes them to the host in its prologue -- the
+// loads in the trip of its first X, the stores while the loading waves wait for the first chunks: this kernel is the
+// one launch of a cycle long enough to hide a trip to the host.  Nothing of the build depends on it.
 template <int NB, int NDM, int LP>
 __global__ __launch_bounds__(M8_THREADS, 1) void jk_m8_kernel(const double* __restrict__ packed, const double* __restrict__ dm,
                                                               const double* __restrict__ wtab, double* __restrict__ jfull,
                                                               double* __restrict__ kpart1, double* __restrict__ kpart2,
                                                               double* __restrict__ jpart, int64_t t_begin, M8Ranges rg, M8Tables tb,
-                                                              int S) {
+                                                              int S, nbx_scalars_courier cr) {
     using G_ = M8Geom<NB, LP>;
     constexpr int N = G_::N, NG = G_::NG, NCH = G_::NCH, BUF = G_::BUF, PT = M4_PROD_THREADS, RING = G_::RING, AHEAD = RING - 1;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -384,6 +389,9 @@ __global__ __launch_bounds__(M8_THREADS, 1) void jk_m8_kernel(const double* __re
         // from registers that were loaded at the first step of tile t - 1 -- a tile may be a single step
         double xq[XH], xp[XH];
         int pbuf0 = p, pbuf1 = -1;  // the row whose p columns each buffer holds
+        const bool courier = blockIdx.x == 0 && wave == 0 && cr.d_partial != nullptr;  // (uniform in the wave)
+        nbx_courier_regs crr;
+        if (courier) nbx_courier_request(cr, lane, crr);
         fetch_xh(q, xq);
         fetch_xh(p, xp);
         store_xh(xs0, 0, xq);
@@ -396,6 +404,7 @@ __global__ __launch_bounds__(M8_THREADS, 1) void jk_m8_kernel(const double* __re
             fetch_xh(px, xp);
             pbuf1 = px;
         }
+        if (courier) nbx_courier_deliver(cr, lane, crr);
         __syncthreads();
         int slot = 0;  // ring slot of the chunk being walked
         for (int t = 0; t < ntile; ++t) {
@@ -590,7 +599,8 @@ struct M8Split {
     M8Tables tb;
     char bad[96];
 };
-static_assert(sizeof(M8Ranges) + sizeof(M8Tables) + 16 * sizeof(void*) <= 4096 - 256, "the argument block of a kernel stays below 4 KB");
+static_assert(sizeof(M8Ranges) + sizeof(M8Tables) + sizeof(nbx_scalars_courier) + 16 * sizeof(void*) <= 4096 - 256,
+              "the argument block of a kernel stays below 4 KB");
 
 template <class G>
 const M8Ranges& m8_ranges(int64_t p0, int64_t np, int* wgs_out, const M8Tables** tb_out = nullptr, const char** bad_out = nullptr) {
@@ -688,7 +698,8 @@ M8Plan m8_plan(int64_t p0, int64_t np, int64_t ndm) {
 
 template <int NB, int LP>
 int m8_run(nbx_ctx* ctx, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm, double* d_jk,
-           void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_wt_in) {
+           void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_wt_in,
+           const nbx_scalars_courier* carry) {
     using G = M8Geom<NB, LP>;
     const int64_t np = p1 - p0, N = G::N, n2 = N * N;
     const M8Plan pl = m8_plan<G>(p0, np, ndm);
@@ -724,6 +735,17 @@ int m8_run(nbx_ctx* ctx, int64_t p0, int64_t p1, const double* d_packed, const d
         NBX_LAUNCH_CHECK();
     }
     const int64_t t_begin = m4_tri((int)p0);
+    // the scalars a deferred cycle left: workgroup 0 carries them (it has tiles whenever the slab has); else their own launch
+    nbx_scalars_courier cr{};
+    if (carry != nullptr && carry->d_partial != nullptr) {
+        if (rg.first[1] > rg.first[0]) {
+            NBX_CHECK_ARG(nbx_courier_valid(*carry));
+            cr = *carry;
+        } else {
+            const int rc = nbx_huz_scalars_flush(ctx, carry);
+            if (rc != NBX_OK) return rc;
+        }
+    }
     {
         nbx_prof_scope prof(ctx, NBX_PROF_JK_DENSE);
         static bool attr_set = false;
@@ -741,10 +763,10 @@ int m8_run(nbx_ctx* ctx, int64_t p0, int64_t p1, const double* d_packed, const d
         }
         if (ndm == 2)
             hipLaunchKernelGGL((jk_m8_kernel<NB, 2, LP>), dim3((unsigned)pl.wgs), dim3(M8_THREADS), pl.lds_bytes, ctx->stream,
-                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, tb, pl.S);
+                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, tb, pl.S, cr);
         else
             hipLaunchKernelGGL((jk_m8_kernel<NB, 1, LP>), dim3((unsigned)pl.wgs), dim3(M8_THREADS), pl.lds_bytes, ctx->stream,
-                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, tb, pl.S);
+                               d_packed, d_dm, wt, d_jk, k1, k2, jp, t_begin, rg, tb, pl.S, cr);
     }
     NBX_LAUNCH_CHECK();
     {  // the two reductions in one launch
@@ -849,9 +871,16 @@ void nbx_jk_m8_weight_layout(int64_t N, int out[4]) {
 // d_wt: NULL, or that table for d_dm: saves the preparation launch
 int nbx_jk_m8(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
               double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_wt) {
+    return nbx_jk_m8_carry(ctx, N, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_wt, nullptr);
+}
+
+// carry: NULL, or the scalars of a deferred SCF cycle for jk_m8_kernel to take to the host on its way (scalars_courier.h)
+int nbx_jk_m8_carry(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
+                    double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_wt,
+                    const nbx_scalars_courier* carry) {
     NBX_CHECK_ARG(nbx_jk_m8_covers(N));
 #define M8_CASE_run(NB_) \
-    case NB_: return m8_run<NB_, M8_LP(NB_)>(ctx, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_wt);
+    case NB_: return m8_run<NB_, M8_LP(NB_)>(ctx, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_wt, carry);
     M8_DISPATCH(N, run)
 #undef M8_CASE_run
     return NBX_E_UNSUPPORTED;

@@ -31,6 +31,18 @@ NBX_JK_BACKEND(nbx_jk_m8_covers, nbx_jk_m8_packed_bytes, nbx_jk_m8_worksize, nbx
 NBX_JK_BACKEND(nbx_jk_mx_covers, nbx_jk_mx_packed_bytes, nbx_jk_mx_worksize, nbx_jk_mx_pack, nbx_jk_mx)
 NBX_JK_BACKEND(nbx_jk_mx_covers_hi, nbx_jk_mx_packed_bytes_hi, nbx_jk_mx_worksize_hi, nbx_jk_mx_pack_hi, nbx_jk_mx_hi)
 #undef NBX_JK_BACKEND
+// jk_m8.hip's run with one more argument: the scalars of a deferred SCF cycle (include/nbx.h nbx_scalars_courier) that its
+// kernel takes to the host in its prologue; NULL: nbx_jk_m8.  The other back-ends carry nothing: a cycle whose next
+// build would run on them is not deferred (nbx_jk_packed_carries), and what arrives anyway is flushed ahead of the build.
+int nbx_jk_m8_carry(nbx_ctx* ctx, int64_t N, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
+                    double* d_jk, void* d_work, const double* d_hv, double* d_fock, double* d_vhf, const double* d_dts,
+                    const nbx_scalars_courier* carry);
+// jk_packed.hip: the whole-tensor build of size nao runs on a kernel that carries (jk_m8.hip, nao its own instance);
+// nbx_jk_packed_fock with the courier
+bool nbx_jk_packed_carries(int64_t nao);
+int nbx_jk_packed_fock_carry(nbx_ctx* ctx, int64_t nao, const double* d_packed, const double* d_dm, const double* d_hv,
+                             double* d_jk, double* d_fock, double* d_vhf, void* d_work, size_t work_bytes,
+                             const double* d_dts, const nbx_scalars_courier* carry);
 // the jk_mx.hip instance N runs as: N itself or the next one, at most eight zero rows and columns more; 0: none
 int64_t nbx_jk_mx_padded(int64_t N);
 

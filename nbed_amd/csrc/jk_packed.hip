@@ -96,7 +96,7 @@ int run_padded(const PackedRoute& r, nbx_ctx* ctx, int64_t nao, int64_t p0, int6
 
 int packed_jk(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d_packed, const double* d_dm, int64_t ndm,
               double* d_jk, void* d_work, size_t work_bytes, const double* d_hv, double* d_fock, double* d_vhf,
-              const double* d_dts) {
+              const double* d_dts, const nbx_scalars_courier* carry = nullptr) {
     NBX_CHECK_ARG(ctx && d_dm && d_jk);
     NBX_CHECK_ARG(nao > 0 && p0 >= 0 && p1 >= p0 && p1 <= nao);
     NBX_CHECK_ARG(d_packed != nullptr || p0 == p1);
@@ -113,6 +113,13 @@ int packed_jk(nbx_ctx* ctx, int64_t nao, int64_t p0, int64_t p1, const double* d
         return NBX_E_NOMEM;
     }
     NBX_CHECK_ARG((reinterpret_cast<uintptr_t>(d_packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0);
+    if (carry != nullptr && carry->d_partial != nullptr) {
+        // a deferred cycle's scalars: on their way with jk_m8.hip's kernel, else by a launch of their own ahead of the build
+        if (r.kernel == NBX_JK_KERNEL_M8 && r.run_as == nao && p1 > p0)
+            return nbx_jk_m8_carry(ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_dts, carry);
+        const int rc = nbx_huz_scalars_flush(ctx, carry);
+        if (rc != NBX_OK) return rc;
+    }
     if (p1 == p0) return nbx_memset(ctx, d_jk, 0, (size_t)((1 + ndm) * nao * nao) * sizeof(double));
     if (r.run_as != nao) return run_padded(r, ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf);
     return BACKENDS[r.kernel].run(ctx, nao, p0, p1, d_packed, d_dm, ndm, d_jk, d_work, d_hv, d_fock, d_vhf, d_dts);
@@ -142,6 +149,18 @@ size_t nbx_jk_dts_layout(int64_t nao, int* nb4, int* lpt4, int* m4) {
     *lpt4 = wl[1];
     *m4 = (wl[2] << 8) | wl[3];
     return m8 ? nbx_jk_m8_weights_bytes(nao) : nbx_jk_m4_weights_bytes(nao);
+}
+
+bool nbx_jk_packed_carries(int64_t nao) {
+    const PackedRoute r = packed_resolve(nao);
+    return r.kernel == NBX_JK_KERNEL_M8 && r.run_as == nao;
+}
+
+int nbx_jk_packed_fock_carry(nbx_ctx* ctx, int64_t nao, const double* d_packed, const double* d_dm, const double* d_hv,
+                             double* d_jk, double* d_fock, double* d_vhf, void* d_work, size_t work_bytes,
+                             const double* d_dts, const nbx_scalars_courier* carry) {
+    NBX_CHECK_ARG(d_hv && d_fock);
+    return packed_jk(ctx, nao, 0, nao, d_packed, d_dm, 2, d_jk, d_work, work_bytes, d_hv, d_fock, d_vhf, d_dts, carry);
 }
 
 extern "C" {

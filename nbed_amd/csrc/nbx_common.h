@@ -79,14 +79,19 @@ inline int64_t nbx_gemm_small_norm_doubles(int64_t m, int64_t n, int64_t batch) 
 int nbx_density_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, int hcore_ndim, const double* d_vemb,
                                const double* d_vhf, const double* d_hz, const double* d_c, int64_t nocc_a, int64_t nocc_b,
                                double* d_dm_out, const double* d_dm_old, double* d_out, const int* d_tail, int64_t tail_n,
-                               double* d_dts);
+                               double* d_dts, nbx_scalars_courier* deferred = nullptr);
 int nbx_diis_update_anti(nbx_ctx* ctx, int64_t n, int64_t space, int64_t slot, int64_t nd, const double* d_x,
                          const double* d_err, int64_t anti_n, double* d_xprev, double* d_xs, double* d_es, double* d_h,
                          double* d_coef);
 int nbx_cycle_scalars_launch(nbx_ctx* ctx, int64_t nao, const double* d_hcore, int hcore_ndim, const double* d_vemb,
                              const double* d_vhf, const double* d_hz, const double* d_dm, const double* d_dm_old,
                              double* d_out, const int* d_tail, int64_t tail_n, double* d_dts, const double* d_dtail,
-                             int64_t dtail_n);
+                             int64_t dtail_n, nbx_scalars_courier* deferred = nullptr);
+// `deferred` (its d_partial set by the caller: room for the launch's partial sums): the kernel stops at its partials --
+// no fence, no arrival counter, no last workgroup, no host store -- and *deferred is filled with what a courier
+// (scalars_courier.h) needs to finish the job later on the same stream.  nbx_cycle_scalars_deferrable: whether the
+// launch for this size is one the courier is written for.
+bool nbx_cycle_scalars_deferrable(int64_t nao, int64_t tail_n);
 // out[b] = A[b]^T - A[b], (batch, nao, nao), out of place
 int nbx_antisym(nbx_ctx* ctx, int64_t nao, int64_t batch, const double* d_a, double* d_out);
 

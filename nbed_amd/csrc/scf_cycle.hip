@@ -10,6 +10,7 @@
 // same order, same operands): results are bit-identical to that path.
 #include <cstdlib>
 
+#include "jk_packed.h"
 #include "nbx_common.h"
 
 // This rank's J/K contribution from the density d_dm_in into st->d_jk: the whole tensor or the slab rows
@@ -33,7 +34,7 @@ static bool huz_whole_tensor(const nbx_huz_state* st) { return st->jk_p0 == 0 &&
 static int huz_cycle_rest(nbx_ctx* ctx, const nbx_huz_state* st, const double* d_dm_in, const double* d_c_in,
                           double* d_dm_out, double* d_c_out, double* d_v_out, double* d_w_out, double* d_hz_out,
                           int mode, int refine_iters, int diis_mode, int diis_slot, int diis_nd, double* h_out,
-                          int* d_status_out);
+                          int* d_status_out, nbx_scalars_courier* deferred = nullptr);
 
 // D[x] = C[x][:, :nocc_x] C[x][:, :nocc_x]^T: the solvers return ascending eigenvalues, so the aufbau-occupied
 // orbitals (get_occ: the n_alpha / n_beta lowest) are the leading columns
@@ -80,18 +81,48 @@ extern "C" int nbx_huz_cycle(nbx_ctx* ctx, const nbx_huz_state* st, const double
                              double* d_dm_out, double* d_c_out, double* d_v_out, double* d_w_out, double* d_hz_out,
                              int mode, int refine_iters, int diis_mode, int diis_slot, int diis_nd, int dts_ready,
                              double* h_out, int* d_status_out) {
+    return nbx_huz_cycle_carry(ctx, st, d_dm_in, d_c_in, d_dm_out, d_c_out, d_v_out, d_w_out, d_hz_out, mode, refine_iters,
+                               diis_mode, diis_slot, diis_nd, dts_ready, h_out, d_status_out, nullptr, 0, nullptr);
+}
+
+// The cycle with the previous cycle's deferred scalars on board of its J/K build (carry) and / or its own scalars left
+// to the next build (defer): include/nbx.h.  Every mode starts with the build, so every mode carries.
+extern "C" int nbx_huz_cycle_carry(nbx_ctx* ctx, const nbx_huz_state* st, const double* d_dm_in, const double* d_c_in,
+                                   double* d_dm_out, double* d_c_out, double* d_v_out, double* d_w_out, double* d_hz_out,
+                                   int mode, int refine_iters, int diis_mode, int diis_slot, int diis_nd, int dts_ready,
+                                   double* h_out, int* d_status_out, const nbx_scalars_courier* carry, int defer,
+                                   nbx_scalars_courier* deferred_out) {
     NBX_CHECK_ARG(ctx && st && d_dm_in && d_dm_out && d_c_out && d_w_out && d_hz_out && h_out);
     NBX_CHECK_ARG(st->nao > 0 && st->d_hv && st->d_ds && st->d_jk && st->d_fock && st->d_vhf && st->d_fock2 &&
                   st->d_jk_work);
+    NBX_CHECK_ARG(defer == 0 || deferred_out != nullptr);
     const int64_t N = st->nao;
     int rc;
+    if (carry != nullptr && carry->d_partial == nullptr) carry = nullptr;
+    // the build that can carry is the one whose successor may be deferred: the 8-fold packed kernel on the whole tensor
+    const bool carrying_build = st->jk_kind == NBX_HUZ_JK_PACKED && huz_whole_tensor(st) && nbx_jk_packed_carries(N);
+    nbx_scalars_courier* deferred = nullptr;
+    if (deferred_out != nullptr) {
+        *deferred_out = nbx_scalars_courier{};
+        if (defer != 0 && carrying_build && st->d_scal_partial != nullptr &&
+            (reinterpret_cast<uintptr_t>(st->d_scal_partial) & 15) == 0 && nbx_cycle_scalars_deferrable(N, 2)) {
+            deferred = deferred_out;
+            deferred->d_partial = st->d_scal_partial;
+        }
+    }
+    if (carry != nullptr && !carrying_build) {  // (the packed route below flushes for itself where its kernel does not carry)
+        rc = nbx_huz_scalars_flush(ctx, carry);
+        if (rc != NBX_OK) return rc;
+        carry = nullptr;
+    }
 
     // ---- Fock build (:156-160)
     if (st->jk_kind == NBX_HUZ_JK_PACKED && huz_whole_tensor(st)) {
         // J/K on the packed integrals with the Fock assembly in its reduction
         NBX_CHECK_ARG(st->d_packed);
-        rc = nbx_jk_packed_fock(ctx, N, st->d_packed, d_dm_in, st->d_hv, st->d_jk, st->d_fock, st->d_vhf, st->d_jk_work,
-                                st->jk_work_bytes, (dts_ready && st->d_dts) ? st->d_dts : nullptr);
+        rc = nbx_jk_packed_fock_carry(ctx, N, st->d_packed, d_dm_in, st->d_hv, st->d_jk, st->d_fock, st->d_vhf,
+                                      st->d_jk_work, st->jk_work_bytes, (dts_ready && st->d_dts) ? st->d_dts : nullptr,
+                                      carry);
         if (rc != NBX_OK) return rc;
     } else {
         // the symmetric kernel on the dense tensor (N < 97; sizes the packed kernel has no instance for) with the Fock assembly
@@ -109,14 +140,15 @@ extern "C" int nbx_huz_cycle(nbx_ctx* ctx, const nbx_huz_state* st, const double
         if (rc != NBX_OK) return rc;
     }
     return huz_cycle_rest(ctx, st, d_dm_in, d_c_in, d_dm_out, d_c_out, d_v_out, d_w_out, d_hz_out, mode, refine_iters,
-                          diis_mode, diis_slot, diis_nd, h_out, d_status_out);
+                          diis_mode, diis_slot, diis_nd, h_out, d_status_out, deferred);
 }
 
-// Everything of a cycle after the Fock matrices st->d_fock / st->d_vhf exist.
+// Everything of a cycle after the Fock matrices st->d_fock / st->d_vhf exist.  deferred (its d_partial set): the
+// scalars kernel stops at its partial sums and *deferred describes the rest for a courier (scalars_courier.h).
 static int huz_cycle_rest(nbx_ctx* ctx, const nbx_huz_state* st, const double* d_dm_in, const double* d_c_in,
                           double* d_dm_out, double* d_c_out, double* d_v_out, double* d_w_out, double* d_hz_out,
                           int mode, int refine_iters, int diis_mode, int diis_slot, int diis_nd, double* h_out,
-                          int* d_status_out) {
+                          int* d_status_out, nbx_scalars_courier* deferred) {
     NBX_CHECK_ARG(mode == 0 || mode == 1 || mode == 2);
     NBX_CHECK_ARG(diis_mode >= 0 && diis_mode <= 2);
     const int64_t N = st->nao, n2 = N * N;
@@ -162,8 +194,8 @@ static int huz_cycle_rest(nbx_ctx* ctx, const nbx_huz_state* st, const double* d
         if (rc != NBX_OK) return rc;
         rc = nbx_gemm(ctx, 'N', 'N', N, N, N, 1.0, st->d_fo, N, n2, st->d_x, N, 0, 0.0, d_dm_out, N, n2, 2);
         if (rc != NBX_OK) return rc;
-        return nbx_huz_cycle_scalars_dts(ctx, N, st->d_hv, 3, nullptr, st->d_vhf, d_hz_out, d_dm_out, d_dm_in, h_out,
-                                         d_status_out, 2, st->d_dts);
+        return nbx_cycle_scalars_launch(ctx, N, st->d_hv, 3, nullptr, st->d_vhf, d_hz_out, d_dm_out, d_dm_in, h_out,
+                                        d_status_out, 2, st->d_dts, nullptr, 0, deferred);
     }
     if (mode == 1) {  // tracked: refine the previous cycle's (eps, C) on the pencil (F, S), no fallback queued
         NBX_CHECK_ARG(d_c_in && st->d_sb && st->d_geig_work && d_status_out);
@@ -194,13 +226,13 @@ static int huz_cycle_rest(nbx_ctx* ctx, const nbx_huz_state* st, const double* d
     static const bool fused_density = getenv("NBX_FUSED_DENSITY") == nullptr || atoi(getenv("NBX_FUSED_DENSITY")) != 0;
     if (fused_density) {
         rc = nbx_density_scalars_launch(ctx, N, st->d_hv, 3, nullptr, st->d_vhf, d_hz_out, d_c_out, st->nocc_a, st->nocc_b,
-                                        d_dm_out, d_dm_in, h_out, d_status, 2, st->d_dts);
+                                        d_dm_out, d_dm_in, h_out, d_status, 2, st->d_dts, deferred);
         if (rc != NBX_E_UNSUPPORTED) return rc;
     }
     rc = cycle_density(ctx, N, st->nocc_a, st->nocc_b, d_c_out, d_dm_out);
     if (rc != NBX_OK) return rc;
-    return nbx_huz_cycle_scalars_dts(ctx, N, st->d_hv, 3, nullptr, st->d_vhf, d_hz_out, d_dm_out, d_dm_in, h_out,
-                                     d_status, 2, st->d_dts);
+    return nbx_cycle_scalars_launch(ctx, N, st->d_hv, 3, nullptr, st->d_vhf, d_hz_out, d_dm_out, d_dm_in, h_out, d_status,
+                                    2, st->d_dts, nullptr, 0, deferred);
 }
 
 // ===================================================================================================== mu-shift

@@ -401,41 +401,60 @@ def _huzinaga_scf(scf_method, embedding_potential, dm_environment_occupied, dm_e
                                     eri=None if packed_d is not None else scf_method.eri_device(), p0=sh.lo, p1=sh.hi)
         reduce = (lambda jk: sh.all_reduce(be, jk)) if split else None
         diis_state = {"first": True, "head": 0, "nd": 0, "space": 6}
-        for i in range(scf_method.max_cycle):
-            if callback is not None:
-                callback(i)
-            out = hstate.sets[i % 3]
-            tracked_now = bool(warm["tracked"] and warm["c"] is not None)
-            purify_now = bool(warm["purify"] and not tracked_now and allow_purify != "0")
-            diis_mode = diis_slot = diis_nd = 0
-            if use_DIIS and i > 1:  # pyscf.lib.diis bookkeeping (scf/diis.py): first update only remembers F
-                if diis_state["first"]:
-                    diis_state["first"] = False
-                    diis_mode = 1
+        # Deferred scalars: the last kernel of a cycle stops at its partial sums and the J/K build of the next cycle takes
+        # them to the host on its way: the kernel's last stage (7 of its 13 us at N = 148) leaves the critical path.
+        # The handle of cycle i is read only after cycle i + 1 -- its courier -- has been queued; wherever
+        # the loop stops queueing it flushes first.  NBED_DEFER_SCALARS=0 (read at every call) switches it off; a backend
+        # without huz_flush (the checker backend) and the split route over several ranks keep the immediate form.
+        defer_kw = ({"defer": True} if reduce is None and hasattr(be, "huz_flush")
+                    and os.environ.get("NBED_DEFER_SCALARS", "1") != "0" else {})
+        if history is not None and hasattr(history, "info"):
+            history.info.update(deferred_scalars=bool(defer_kw))
+        try:
+            for i in range(scf_method.max_cycle):
+                if callback is not None:
+                    callback(i)
+                out = hstate.sets[i % 3]
+                tracked_now = bool(warm["tracked"] and warm["c"] is not None)
+                purify_now = bool(warm["purify"] and not tracked_now and allow_purify != "0")
+                diis_mode = diis_slot = diis_nd = 0
+                if use_DIIS and i > 1:  # pyscf.lib.diis bookkeeping (scf/diis.py): first update only remembers F
+                    if diis_state["first"]:
+                        diis_state["first"] = False
+                        diis_mode = 1
+                    else:
+                        if diis_state["head"] >= diis_state["space"]:
+                            diis_state["head"] = 0
+                        diis_slot = diis_state["head"]
+                        diis_state["head"] += 1
+                        diis_state["nd"] = min(diis_state["nd"] + 1, diis_state["space"])
+                        diis_mode, diis_nd = 2, diis_state["nd"]
+                if purify_now:  # density by purification: this cycle has no orbitals, X F X is left in out["v"]
+                    pending_now = be.huz_cycle(hstate, dm_d, None, out, 2, warm["pur_iters"], diis_mode, diis_slot, diis_nd,
+                                               dts_ready, reduce=reduce, **defer_kw)
+                    warm["c"] = warm["v"] = None
                 else:
-                    if diis_state["head"] >= diis_state["space"]:
-                        diis_state["head"] = 0
-                    diis_slot = diis_state["head"]
-                    diis_state["head"] += 1
-                    diis_state["nd"] = min(diis_state["nd"] + 1, diis_state["space"])
-                    diis_mode, diis_nd = 2, diis_state["nd"]
-            if purify_now:  # density by purification: this cycle has no orbitals, X F X is left in out["v"]
-                pending_now = be.huz_cycle(hstate, dm_d, None, out, 2, warm["pur_iters"], diis_mode, diis_slot, diis_nd,
-                                           dts_ready, reduce=reduce)
-                warm["c"] = warm["v"] = None
-            else:
-                c_in = warm["c"] if tracked_now else warm["v"]
-                pending_now = be.huz_cycle(hstate, dm_d, c_in, out, tracked_now, warm["iters"], diis_mode, diis_slot,
-                                           diis_nd, dts_ready, reduce=reduce)
-                warm["c"] = out["c"]
-                if not tracked_now:
-                    warm["v"] = out["v"]
-            dts_ready = dts_d is not None
-            dm_d, hz, c_d, mo_energy_h = out["dm"], out["hz"], out["c"], out["w"]
-            state_now = (i, pending_now, out["c"], out["w"], out["dm"], out["hz"], tracked_now, purify_now, out["v"])
-            if pending is not None and judge(pending):
-                break
-            pending = state_now
+                    c_in = warm["c"] if tracked_now else warm["v"]
+                    pending_now = be.huz_cycle(hstate, dm_d, c_in, out, tracked_now, warm["iters"], diis_mode, diis_slot,
+                                               diis_nd, dts_ready, reduce=reduce, **defer_kw)
+                    warm["c"] = out["c"]
+                    if not tracked_now:
+                        warm["v"] = out["v"]
+                dts_ready = dts_d is not None
+                dm_d, hz, c_d, mo_energy_h = out["dm"], out["hz"], out["c"], out["w"]
+                state_now = (i, pending_now, out["c"], out["w"], out["dm"], out["hz"], tracked_now, purify_now, out["v"])
+                if pending is not None and judge(pending):
+                    break
+                pending = state_now
+        except BaseException:
+            if defer_kw:  # (a raised restart: the last cycle queued has no courier; a failure here must not hide the cause)
+                try:
+                    be.huz_flush(hstate)
+                except Exception:  # noqa: BLE001
+                    logger.debug("flush of the deferred scalars failed behind an exception", exc_info=True)
+            raise
+        if defer_kw:
+            be.huz_flush(hstate)  # (convergence, max_cycle: the last cycle queued has no courier)
 
     for i in range(0 if use_cycle_call else scf_method.max_cycle):
         if callback is not None:
